@@ -34,7 +34,12 @@ Defaults (round 4): the AIR is the synthetic constraints bloated to triton-air's
 claim words are given as twenty-first's in-memory Montgomery words (--input-form montgomery: the
 form the Rust drop-in hands over without a copy; converted on the host before anything is timed).
 
-Beside `value` (HBM-resident input, the contract):
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what `value` needs: it sets up, warms
+up, times the K steps, writes the last step's outputs when --dump-outputs DIR is given (dump_outputs)
+and prints the result line (`ms_per_step`: the milliseconds one timed step took).  Everything below
+runs with --full only.
+
+Beside `value` (HBM-resident input, the contract), with --full:
   roofline: the dominant kernel, the per-level Merkle hash launches (k_mp_hash), as Tip5 VALU
     lane-ops/s against the gfx950 VALU peak, from its launches in steps run one at a time right
     after the timed region (the kernel's own rate: launches x average <= step time).
@@ -60,7 +65,7 @@ Beside `value` (HBM-resident input, the contract):
     profiles/LATEST, attached only when profiles/<tag>/LIB_SHA256 is the hash of the library this run
     loaded; every fraction of a ceiling is asserted <= 1.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config {3,4,5}]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config {3,4,5}] [--full] [--dump-outputs DIR]
        python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -339,6 +344,34 @@ def pipelined(batches, steps: int, inflight: int, expect):
     return time.perf_counter() - t, ok
 
 
+DUMP_TRANSCRIPTS = 64  # proofs whose device-derived transcripts --dump-outputs writes
+
+
+def dump_outputs(out_dir: str, batch, verdicts, batch_ok) -> None:
+    """--dump-outputs: what the last timed step computed, as float32 / float64 .npy files (the inputs
+    are seeded, so two builds of the library can be compared file for file):
+      verdicts.npy       float32 [n]: the per-proof verdicts nhip_batch_wait returned (1 accept, 0 reject)
+      batch_verdict.npy  float32 [1]: the batch verdict returned with them
+      transcript_sample_proofs.npy  float64: the proofs sampled below (min(n, 64), seed 0xD0)
+      transcript_sample.npy  float64 [k, 2]: for each sampled proof, in order, [proof index, fail phase,
+        XFE samples, every Fiat-Shamir sample (3 words each), the FRI indices] as the device derived
+        them in that step (nhip_batch_transcript of the step's batch, which has not been launched
+        since); every u64 word as its (low, high) 32-bit halves, exact in float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    v = np.asarray(verdicts)
+    np.save(os.path.join(out_dir, "verdicts.npy"), v.astype(np.float32))
+    np.save(os.path.join(out_dir, "batch_verdict.npy"), np.array([1.0 if batch_ok else 0.0], dtype=np.float32))
+    pick = np.sort(np.random.default_rng(0xD0).choice(v.size, size=min(v.size, DUMP_TRANSCRIPTS), replace=False))
+    words = []
+    for i in pick.tolist():
+        xs, idx, fail = batch.transcript(i)
+        words += [i, fail, len(xs)] + [w for x in xs for w in x] + [int(j) for j in idx]
+    w = np.array(words, dtype=np.uint64)
+    np.save(os.path.join(out_dir, "transcript_sample_proofs.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, "transcript_sample.npy"),
+            np.stack([(w & np.uint64(0xFFFFFFFF)).astype(np.float64), (w >> np.uint64(32)).astype(np.float64)], axis=1))
+
+
 # resident one-stream batches (<= SINGLE_STREAM_MAX_PROOFS) replay their launches from a HIP graph
 # (nhip_batch_set_graph): config 5's 64 / 8 proofs +3.5% / +5% at 20 in flight; a two-stream batch's
 # graph measured slower (512 proofs -12%: profiles/r06/ab_graphs.txt), so those launch directly
@@ -394,7 +427,8 @@ def hw_queues_wanted(inflight: int, multi_rank: bool, streams: int = 2) -> int:
 def load_pool4():
     """The 256 distinct accepting proofs config 4 draws from (oracle/pool4.py: the 5 committed full
     proofs of c3_pool.npz + 251 sparse-prover proofs, distinct claims and seeds, every one verified
-    by both oracles, with its oracle transcript), built once per machine outside the timed region."""
+    by both oracles, with its oracle transcript), built once per checkout (by build(), under
+    oracle/_pool/) outside the timed region."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import pool4  # test-data generator (proof construction only)
     return pool4.load()
@@ -1246,7 +1280,17 @@ def main():
                     help="R > 1: R resident copies of the batch in rotation, up to R steps in flight (step k+1 is "
                          "launched before step k is waited on, so its row hashing fills step k's latency-bound "
                          "phases). Default: 2 for >= 4,096 proofs per GPU, 8 below (profiles/r03j)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the kernel-timing passes (roofline), the committed "
+                         "PMC figures, the CPU baseline and every leg (product depth, share_n8, pcie_inclusive, "
+                         "tip5_paths, queue, config5, config1_latency, hw_queues_4, group_stream, node); without it "
+                         "a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's per-proof "
+                         "verdicts, the batch verdict) and the Fiat-Shamir transcripts the device derived in that "
+                         "step for a fixed sample of its proofs as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    full = args.full
 
     plan = launch_plan(args.gpus, os.environ, sys.argv[1:],
                        n_visible=_visible_gpus() if args.gpus > 1 and not os.environ.get("WORLD_SIZE") else None,
@@ -1303,6 +1347,8 @@ def main():
     R = args.inflight or default_inflight(n, gpu_exchange)
     # before anything initialises HIP (nothing above has)
     want_q = hw_queues_wanted(R, gpu_exchange, streams_for(n))
+    # (the two legs' depths count with or without --full: the timed region runs at the same hardware
+    # queue provisioning either way)
     if world == 1 and args.config == 4 and total == 4096 and args.share_steps > 0:
         # the share_n8 leg runs the N = 8 rank's 512-proof share at its own depth in this process
         want_q = max(want_q, hw_queues_wanted(default_inflight(total // 8), False))
@@ -1314,11 +1360,12 @@ def main():
     elif int(os.environ.get("GPU_MAX_HW_QUEUES", "0") or 0) < want_q:
         os.environ["GPU_MAX_HW_QUEUES"] = str(want_q)
     hwq4 = None
-    if world == 1 and args.hwq4_steps > 0 and not os.environ.get("NHIP_BENCH_HWQ"):
+    if full and world == 1 and args.hwq4_steps > 0 and not os.environ.get("NHIP_BENCH_HWQ"):
         # a child process, started before this one touches the GPU: the same workload with every
         # stream on HIP's default 4 hardware queues (the library's own provisioning is overridden)
         import subprocess
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", str(args.config), "--steps", str(args.hwq4_steps),
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", str(args.config),
+               "--steps", str(args.hwq4_steps),
                "--warmup", str(min(args.warmup, 10)), "--no-cpu", "--paths-log2", "0", "--stream-batches", "0",
                "--config1-seconds", "0", "--iso-steps", "0", "--hwq4-steps", "0", "--air", args.air,
                "--input-form", args.input_form, "--group-batches", "0"]
@@ -1335,7 +1382,7 @@ def main():
                 "measured": "child process before this one initialised HIP, same workload, NHIP_BENCH_HWQ=4"}
         log(f"[hwq4] {h['value']:.0f} proofs/s at 4 hardware queues ({time.time() - t:.1f}s)")
     rank_path = None
-    if (world == 1 and args.config == 4 and total == 4096 and args.share_steps > 0 and args.rank_path
+    if (full and world == 1 and args.config == 4 and total == 4096 and args.share_steps > 0 and args.rank_path
             and not os.environ.get("NHIP_BENCH_FORCE_DIST")):
         # the N = 8 rank's share size through the multi-rank path itself (process group, host
         # exchange, one RCCL all-reduce after the region) at world size 1: a child under
@@ -1347,14 +1394,17 @@ def main():
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
-               "--gpus", "1", "--proofs", str(total // 8), "--steps", str(args.share_steps), "--warmup",
+               "--full", "--gpus", "1", "--proofs", str(total // 8), "--steps", str(args.share_steps), "--warmup",
                str(args.warmup), "--no-cpu", "--paths-log2", "0", "--stream-batches", "0", "--group-batches", "0",
                "--config1-seconds", "0", "--product-steps", "0", "--share-steps", "0", "--queue-callers", "0",
                "--config5-proofs", "0", "--air", args.air, "--input-form", args.input_form]
         t = time.time()
         try:
             out = subprocess.run(cmd, env=dict(os.environ, NHIP_BENCH_FORCE_DIST="1"), stdout=subprocess.PIPE,
-                                 stderr=subprocess.DEVNULL, timeout=600, check=True)
+                                 stderr=subprocess.PIPE, timeout=600)
+            if out.returncode != 0:  # a crash of the multi-rank path: shown, and the run fails (exit 1)
+                log(f"[rank path] child exited {out.returncode}:\n" + out.stderr.decode(errors="replace")[-2000:])
+                raise subprocess.CalledProcessError(out.returncode, cmd[:4])
             h = json.loads(out.stdout.decode().strip().splitlines()[-1])
             rank_path = {"value": h["value"], "ms_per_step": h["ms_per_step"], "steps": h["steps"],
                          "inflight": h["inflight"], "verdicts_correct": h["verdicts_correct"],
@@ -1365,8 +1415,9 @@ def main():
             log(f"[rank path] {h['value']:.0f} proofs/s ({time.time() - t:.1f}s)")
         except (subprocess.SubprocessError, ValueError, KeyError, IndexError) as e:
             rank_path = {"error": f"{type(e).__name__}: {e}"[:300]}
+            log(f"[rank path] failed: {rank_path['error']}")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         t = time.time()
         cpu = cpu_baseline(air_words, claims, proofs, expect, args.cpu_seconds, args.cpu_threads)
         log(f"[cpu] {cpu['value']:.1f} proofs/s ({time.time() - t:.1f}s)")
@@ -1428,6 +1479,7 @@ def main():
     launched = []   # ring slots in flight, oldest first
     next_slot = [0]
     to_launch = [0]  # launches left in the current region: each region starts and ends with nothing in flight
+    last_waited = [None]  # the batch of the last completed step (--dump-outputs reads its transcripts)
     # configs 4 / 5 with several ranks: one all-gather per step carries every rank's batch verdict
     # and per-proof verdicts (shard.VerdictExchange), posted without waiting and completed one step
     # later; config 3 (no per-proof exchange): the all-reduce(MIN) of the batch verdict
@@ -1458,6 +1510,7 @@ def main():
             launch_one()
         b = ring[launched.pop(0)]
         v, ok = b.wait()
+        last_waited[0] = b
         if timeline is not None:
             timeline.append(("W", time.perf_counter()))
         st = b.stats()
@@ -1512,51 +1565,56 @@ def main():
         with open(os.environ["NHIP_BENCH_TIMELINE"], "w") as f:
             json.dump({"t_start": t_start, "elapsed": elapsed, "inflight": R,
                        "events": [(k, t - t_start) for k, t in timeline]}, f)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # the last timed step's batch is not launched again before this (the region ended with nothing in flight)
+        dump_outputs(args.dump_outputs, last_waited[0], v, batch_ok)
     if exch is not None:
         correct = correct and len(exchanged) == args.steps
-        for ok_all, full in exchanged:
-            correct = correct and bool((full.astype(bool) == expect_all).all())
+        for ok_all, v_all in exchanged:
+            correct = correct and bool((v_all.astype(bool) == expect_all).all())
             batch_ok = ok_all
     # the kernel-timing passes, right after the timed region (which ran the product's configuration,
     # without per-dispatch timestamps): the same R-in-flight shape again with them
     # (roofline.inflight), then the same steps one at a time (roofline, the kernel's own rate)
-    kernel_timing(ring, True)
-    acc_if, if_steps = {}, max(1, min(args.steps, 50))
-    ctx.synchronize()
-    t_if = time.perf_counter()
-    q_if, launched_if, ok_if = [], 0, True
-    for i in range(min(R, if_steps)):
-        ring[i].launch()
-        q_if.append(i)
-        launched_if += 1
-    while q_if:
-        i = q_if.pop(0)
-        v_if, _ = ring[i].wait()
-        for k, x in ring[i].stats().items():  # before the relaunch re-records the events
-            acc_if[k] = acc_if.get(k, 0.0) + x
-        if launched_if < if_steps:
+    # (--full only: they are runs of their own)
+    acc_if, if_steps, if_ms = {}, max(1, min(args.steps, 50)), 0.0
+    acc_iso, iso_ms = {}, 0.0
+    iso_steps = args.iso_steps
+    if full:
+        kernel_timing(ring, True)
+        ctx.synchronize()
+        t_if = time.perf_counter()
+        q_if, launched_if, ok_if = [], 0, True
+        for i in range(min(R, if_steps)):
             ring[i].launch()
             q_if.append(i)
             launched_if += 1
-        ok_if = ok_if and bool((np.asarray(v_if, dtype=bool) == expect).all())
-    if_ms = (time.perf_counter() - t_if) / if_steps * 1e3
-    correct = correct and ok_if
-    acc_iso, iso_ms = {}, 0.0
-    iso_steps = args.iso_steps
-    if R > 1 and iso_steps:
-        t_iso = time.perf_counter()
-        for _ in range(iso_steps):
-            ring[0].launch()
-            ring[0].wait()
-            for k, x in ring[0].stats().items():
-                acc_iso[k] = acc_iso.get(k, 0.0) + x
-        iso_ms = (time.perf_counter() - t_iso) / iso_steps * 1e3
-    kernel_timing(ring, False)
+        while q_if:
+            i = q_if.pop(0)
+            v_if, _ = ring[i].wait()
+            for k, x in ring[i].stats().items():  # before the relaunch re-records the events
+                acc_if[k] = acc_if.get(k, 0.0) + x
+            if launched_if < if_steps:
+                ring[i].launch()
+                q_if.append(i)
+                launched_if += 1
+            ok_if = ok_if and bool((np.asarray(v_if, dtype=bool) == expect).all())
+        if_ms = (time.perf_counter() - t_if) / if_steps * 1e3
+        correct = correct and ok_if
+        if R > 1 and iso_steps:
+            t_iso = time.perf_counter()
+            for _ in range(iso_steps):
+                ring[0].launch()
+                ring[0].wait()
+                for k, x in ring[0].stats().items():
+                    acc_iso[k] = acc_iso.get(k, 0.0) + x
+            iso_ms = (time.perf_counter() - t_iso) / iso_steps * 1e3
+        kernel_timing(ring, False)
 
     # the product's own pipeline depth beside the bench's: a queue or a group member keeps two
     # batches in flight (two slots), with the library's recommended hardware queues enough for it
     product = None
-    if world == 1 and R > 2 and args.product_steps > 0:
+    if full and world == 1 and R > 2 and args.product_steps > 0:
         ctx.synchronize()
         dt, ok2 = pipelined(ring, args.product_steps, 2, expect)
         product = {"value": total * args.product_steps / dt, "unit": "proofs/s", "inflight": 2,
@@ -1625,8 +1683,8 @@ def main():
     # other kernels (launches x average <= R x step time only): how the level launches share the
     # machine, not the kernel's rate.  kernel_avg_ms_events: the HIP-event span of one step's
     # back-to-back hash launches / launches (adds the dispatch gaps between levels).
-    traffic, traffic_tag = pmc_traffic("k_mp_hash", args.config, len(proofs))
-    mp_valu, mp_valu_tag = pmc_mp_valu_per_launch(args.config, len(proofs))
+    traffic, traffic_tag = pmc_traffic("k_mp_hash", args.config, len(proofs)) if full else (None, None)
+    mp_valu, mp_valu_tag = pmc_mp_valu_per_launch(args.config, len(proofs)) if full else (None, None)
 
     def roofline(a, steps, step_ms_, overlap, measured):
         a = {k: v / steps for k, v in a.items()}
@@ -1726,54 +1784,56 @@ def main():
         "inflight": R,
         "iso_steps": iso_steps if acc_iso else 0,
     }
-    inflight = roofline(acc_if, if_steps, if_ms, R,
-                        f"{if_steps} steps right after the timed region, {R} in flight as there (launches of "
-                        f"different steps overlap); per-launch HIP events (hipExtLaunchKernel start/stop)")
-    # that pass's own rate beside the timed region's: the cost of the per-dispatch timestamps
-    inflight["proofs_per_s_gpu_timed_region"] = n * K / elapsed
-    inflight["proofs_per_s_gpu_with_dispatch_timestamps"] = n / (if_ms / 1e3)
-    inflight["pass_steps"] = if_steps
-    if acc_iso:
-        res["roofline"] = roofline(acc_iso, iso_steps, iso_ms, 1,
-                                   f"the kernel's own rate: {iso_steps} steps one at a time right after the timed "
-                                   f"region; per-launch HIP events (hipExtLaunchKernel start/stop)")
-        if gpu_shared:  # ranks time-sharing one GPU (a rehearsal): the other ranks' steps stretch these
-            res["roofline"]["gpu_shared_by_ranks"] = world
+    if full:  # the kernel-timing passes' figures
+        inflight = roofline(acc_if, if_steps, if_ms, R,
+                            f"{if_steps} steps right after the timed region, {R} in flight as there (launches of "
+                            f"different steps overlap); per-launch HIP events (hipExtLaunchKernel start/stop)")
+        # that pass's own rate beside the timed region's: the cost of the per-dispatch timestamps
+        inflight["proofs_per_s_gpu_timed_region"] = n * K / elapsed
+        inflight["proofs_per_s_gpu_with_dispatch_timestamps"] = n / (if_ms / 1e3)
+        inflight["pass_steps"] = if_steps
+        if acc_iso:
+            res["roofline"] = roofline(acc_iso, iso_steps, iso_ms, 1,
+                                       f"the kernel's own rate: {iso_steps} steps one at a time right after the timed "
+                                       f"region; per-launch HIP events (hipExtLaunchKernel start/stop)")
+            if gpu_shared:  # ranks time-sharing one GPU (a rehearsal): the other ranks' steps stretch these
+                res["roofline"]["gpu_shared_by_ranks"] = world
+            else:
+                assert res["roofline"]["launches_x_avg_ms"] <= step_ms, (res["roofline"], step_ms)
+            # the row-hashing launch of the same isolated steps (k_hash_rows: one lane per revealed row,
+            # every main / aux / quotient row's hash_varlen; dispatch begin / end events), beside the
+            # Merkle launches: permutations per launch = proofs x checks x sum over the three trees of
+            # (width // 10 + 1), priced at the same 7,520 lane-ops per permutation
+            rows_ms = acc_iso.get("ms_row_hash_exec", 0.0) / iso_steps
+            if rows_ms > 0:
+                widths = (stark.num_main, 3 * stark.num_aux, 3 * stark.num_quotient_segments)
+                rows_perms = n * stark.num_collinearity_checks * sum(w // 10 + 1 for w in widths)
+                ach = rows_perms * TIP5_VALU_OPS_PER_PERM / (rows_ms / 1e3)
+                res["roofline"]["rows_kernel"] = {
+                    "kernel": "k_hash_rows", "kernel_avg_ms": rows_ms, "perms_per_launch": rows_perms,
+                    "achieved": ach / 1e12, "frac": ach / VALU_PEAK_LANE_OPS,
+                    "frac_of_measured_ceiling": ach / (VALU_ISSUE_CEILING * 64),
+                    "row_bytes_per_launch": n * stark.num_collinearity_checks * sum(widths) * 8,
+                    "measured": f"the same {iso_steps} isolated steps; hipExtLaunchKernel start/stop of the row launch"}
+                rv, rv_tag = pmc_rows_valu_per_launch(args.config, len(proofs))
+                if rv:
+                    # a row permutation skips its capacity-only / digest-only last-round outputs, so it
+                    # executes fewer than the fixed 7,520: the executed count (committed PMC pass of this
+                    # library) against the measured issue ceiling is the kernel's own issue fraction
+                    ex = rv * 64 / rows_perms
+                    res["roofline"]["rows_kernel"].update({
+                        "valu_ops_per_perm_executed": ex, "executed_profile": rv_tag,
+                        "executed_frac_of_measured_ceiling":
+                        rows_perms * ex / (rows_ms / 1e3) / (VALU_ISSUE_CEILING * 64)})
+            res["roofline"]["inflight"] = {k: inflight[k] for k in ("achieved", "frac", "kernel_avg_ms",
+                                                                     "kernel_avg_ms_events", "launches_per_step",
+                                                                     "perms_per_launch", "launches_x_avg_ms", "step_ms",
+                                                                     "measured", "proofs_per_s_gpu_timed_region",
+                                                                     "proofs_per_s_gpu_with_dispatch_timestamps",
+                                                                     "pass_steps")}
         else:
-            assert res["roofline"]["launches_x_avg_ms"] <= step_ms, (res["roofline"], step_ms)
-        # the row-hashing launch of the same isolated steps (k_hash_rows: one lane per revealed row,
-        # every main / aux / quotient row's hash_varlen; dispatch begin / end events), beside the
-        # Merkle launches: permutations per launch = proofs x checks x sum over the three trees of
-        # (width // 10 + 1), priced at the same 7,520 lane-ops per permutation
-        rows_ms = acc_iso.get("ms_row_hash_exec", 0.0) / iso_steps
-        if rows_ms > 0:
-            widths = (stark.num_main, 3 * stark.num_aux, 3 * stark.num_quotient_segments)
-            rows_perms = n * stark.num_collinearity_checks * sum(w // 10 + 1 for w in widths)
-            ach = rows_perms * TIP5_VALU_OPS_PER_PERM / (rows_ms / 1e3)
-            res["roofline"]["rows_kernel"] = {
-                "kernel": "k_hash_rows", "kernel_avg_ms": rows_ms, "perms_per_launch": rows_perms,
-                "achieved": ach / 1e12, "frac": ach / VALU_PEAK_LANE_OPS,
-                "frac_of_measured_ceiling": ach / (VALU_ISSUE_CEILING * 64),
-                "row_bytes_per_launch": n * stark.num_collinearity_checks * sum(widths) * 8,
-                "measured": f"the same {iso_steps} isolated steps; hipExtLaunchKernel start/stop of the row launch"}
-            rv, rv_tag = pmc_rows_valu_per_launch(args.config, len(proofs))
-            if rv:
-                # a row permutation skips its capacity-only / digest-only last-round outputs, so it
-                # executes fewer than the fixed 7,520: the executed count (committed PMC pass of this
-                # library) against the measured issue ceiling is the kernel's own issue fraction
-                ex = rv * 64 / rows_perms
-                res["roofline"]["rows_kernel"].update({
-                    "valu_ops_per_perm_executed": ex, "executed_profile": rv_tag,
-                    "executed_frac_of_measured_ceiling": rows_perms * ex / (rows_ms / 1e3) / (VALU_ISSUE_CEILING * 64)})
-        res["roofline"]["inflight"] = {k: inflight[k] for k in ("achieved", "frac", "kernel_avg_ms",
-                                                                 "kernel_avg_ms_events", "launches_per_step",
-                                                                 "perms_per_launch", "launches_x_avg_ms", "step_ms",
-                                                                 "measured", "proofs_per_s_gpu_timed_region",
-                                                                 "proofs_per_s_gpu_with_dispatch_timestamps",
-                                                                 "pass_steps")}
-    else:
-        res["roofline"] = inflight
-    valu_step, valu_tag = pmc_valu_per_step(args.config, len(proofs))
+            res["roofline"] = inflight
+    valu_step, valu_tag = pmc_valu_per_step(args.config, len(proofs)) if full else (None, None)
     if valu_step:
         # the whole pipeline against the measured VALU issue ceiling: committed PMC instruction
         # count of one step (per GPU) / this run's step time
@@ -1791,7 +1851,7 @@ def main():
     step_s = elapsed / K
     res["hbm"] = {"proof_bytes_per_step": words_step * 8, "achieved_GBps": words_step * 8 / step_s / 1e9,
                   "peak_GBps": HBM_PEAK / 1e9, "frac": words_step * 8 / step_s / HBM_PEAK}
-    bytes_step, bytes_tag = pmc_bytes_per_step(args.config, len(proofs))
+    bytes_step, bytes_tag = pmc_bytes_per_step(args.config, len(proofs)) if full else (None, None)
     if bytes_step:
         res["hbm"].update({"pmc_bytes_per_step": bytes_step, "pmc_GBps": bytes_step / step_s / 1e9,
                            "pmc_frac": bytes_step / step_s / HBM_PEAK, "pmc_profile": bytes_tag})
@@ -1803,7 +1863,7 @@ def main():
     # the N = 8 rank's share on this GPU (rank 0 of 8's LPT shard of the same 4,096-proof job), in
     # the same command's shape (its own ring, warm-up, `steps` timed steps): what each GPU of the
     # driver's 8-GPU run does, measured on one
-    if world == 1 and args.config == 4 and total == 4096 and args.share_steps > 0:
+    if full and world == 1 and args.config == 4 and total == 4096 and args.share_steps > 0:
         sc, sp, se, _, _, _ = make_config4(pool4, total, 0.01, 8, 0)
         scl, spr = device_form(sc, sp, mont)
         sn = [NS.Claim(*c) for c in scl]
@@ -1830,25 +1890,27 @@ def main():
             if "value" in rank_path:
                 rank_path["vs_value_per_proof"] = rank_path["value"] / res["value"]
                 correct = correct and rank_path["verdicts_correct"]
+            else:
+                correct = False  # the child crashed or printed no result line (logged above, `error` in the line)
             sh["rank_path"] = rank_path
         res["share_n8"] = sh
         correct = correct and ok3
     _assert_fracs(res)
     # the PCIe-inclusive leg and the config-2 microbench belong to the one-GPU report (N = 1): with
     # several ranks, rank 0 would run them alone while the others tear down
-    if args.stream_batches > 0 and not gpu_shared:
+    if full and args.stream_batches > 0 and not gpu_shared:
         # every rank at once (its shard to its own GPU): the multi-process form of the node's feed
         pc = pcie_stream(ctx, gair, stark, dev_claims, dev_proofs, expect, args.stream_batches, dist, total)
         res["pcie_inclusive"] = pc
         correct = correct and pc["verdicts_correct"] is not False  # None: the leg raised (reported in it)
-    if world == 1 and args.paths_log2 > 0:
+    if full and world == 1 and args.paths_log2 > 0:
         res["tip5_paths"] = tip5_paths(ctx, args.paths_log2, 5)
-    if world == 1 and args.queue_callers > 0:
+    if full and world == 1 and args.queue_callers > 0:
         t = time.time()
         res["queue"] = queue_leg(ctx, gair, stark, dev_claims, dev_proofs, expect, args.queue_callers)
         correct = correct and res["queue"]["verdicts_correct"]
         log(f"[queue] {res['queue']['value']:.0f} proofs/s ({time.time() - t:.1f}s)")
-    if world == 1 and args.config5_proofs > 0:
+    if full and world == 1 and args.config5_proofs > 0:
         t = time.time()
         res["config5"] = config5_leg(ctx, gair, stark, args.config5_proofs, inflight=args.config5_inflight)
         correct = correct and res["config5"]["verdicts_correct"]
@@ -1864,7 +1926,7 @@ def main():
                 res["config5"]["share_n8"]["target"] = CONFIG5_SHARE_TARGET
                 res["config5"]["share_n8"]["meets_target"] = sh5["value"] >= CONFIG5_SHARE_TARGET
         log(f"[config5] {res['config5']['value']:.0f} proofs/s ({time.time() - t:.1f}s)")
-    if world == 1 and args.config1_seconds > 0 and not args.no_cpu:
+    if full and world == 1 and args.config1_seconds > 0 and not args.no_cpu:
         res["config1_latency"] = config1_latency(ctx, gair, stark, air_words, args.config1_seconds)
         correct = correct and res["config1_latency"]["verdict_accept"]
     if cpu is not None:
@@ -1874,7 +1936,7 @@ def main():
         correct = correct and hwq4["verdicts_correct"]
     # the in-process multi-GPU form (one process, nhip_group_stream over every GPU of the job): rank
     # 0 drives all of them while the other ranks wait on the host with their batches freed
-    if args.group_batches > 0 and args.config == 4 and not under_profiler():
+    if full and args.group_batches > 0 and args.config == 4 and not under_profiler():
         if dist is not None:
             dist.barrier()  # every rank's batches are closed
 

@@ -13,8 +13,8 @@ distinct accepting proofs, in the mix's proportions (heights 9 / 10 / 11 / 12 / 
 Every proof is verified by both oracle restatements (oracle/stark_ref.py, oracle/stark_oracle.c)
 before the pool is written (all accept), and the Python oracle's Fiat-Shamir transcript of each
 (every squeezed sample, the FRI indices) is kept with it for the GPU transcript comparison.  The pool is built in a child process (a pool of forked workers, none of which has touched a
-GPU) and cached under the system temp directory, keyed by the generator sources and the c3 pool, so
-the bench and the GPU tests of one machine build it once.  Used by bench.py (config 4) and
+GPU) and cached under oracle/_pool/ (cache_dir), keyed by the generator sources and the c3 pool:
+build() of __graft_entry__.py makes it, so the bench and the GPU tests find it there.  Used by bench.py (config 4) and
 tests/test_gpu_config4.py; never by the product.
 
 Usage: python oracle/pool4.py --out PATH [--workers N]
@@ -139,12 +139,29 @@ def _key() -> str:
     return h.hexdigest()[:16]
 
 
+def cache_dir() -> str:
+    """oracle/_pool/ in this tree (kept out of git), where build() of __graft_entry__.py leaves the
+    pool for the bench and the GPU tests.  A tree that cannot be written (a read-only install) falls
+    back to the system temp directory, and says so on stderr: the pool is then built by the first
+    run that needs it."""
+    d = os.path.join(HERE, "_pool")
+    try:
+        os.makedirs(d, exist_ok=True)
+        if os.access(d, os.W_OK):
+            return d
+    except OSError:
+        pass
+    tmp = tempfile.gettempdir()
+    print(f"pool4: {d} cannot be written; caching the config-4 pool under {tmp}", file=sys.stderr, flush=True)
+    return tmp
+
+
 def load(workers: int | None = None, timeout_s: float = 1800.0) -> dict:
-    """The pool (building it once per machine): {"air", "proofs", "claims", "heights", "main_rows",
+    """The pool (building it once per checkout): {"air", "proofs", "claims", "heights", "main_rows",
     "kind"}.  The first caller builds it in a child process; concurrent callers (the ranks of one
     node) wait for the file."""
     workers = workers or min(16, os.cpu_count() or 1)
-    path = os.path.join(tempfile.gettempdir(), f"nhip_pool4_{_key()}.npz")
+    path = os.path.join(cache_dir(), f"nhip_pool4_{_key()}.npz")
     lock = path + ".lock"
     if not os.path.exists(path):
         try:

@@ -211,3 +211,139 @@ def test_tx_stream_is_what_the_node_leg_decodes():
     assert pos == buf.size and len(got) == len(proofs)
     for a, b in zip(got, proofs):
         assert np.array_equal(np.asarray(a, dtype=np.uint64), np.asarray(b, dtype=np.uint64))
+
+
+def test_dump_outputs_files(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 / float64 .npy files; the u64 transcript words
+    of a fixed, seeded sample of proofs as exact (low, high) 32-bit halves; the same files twice."""
+    import numpy as np
+
+    class FakeBatch:
+        def transcript(self, i):
+            return [(i, (1 << 64) - 1, 3)] * (2 + i % 3), list(range(80)), i % 2
+
+    v = np.random.default_rng(1).integers(0, 2, 200).astype(np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), FakeBatch(), v, False)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["batch_verdict.npy", "transcript_sample.npy", "transcript_sample_proofs.npy", "verdicts.npy"]
+    got = {n: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert got[n].dtype in (np.float32, np.float64)
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / n))
+    assert np.array_equal(got["verdicts.npy"], v.astype(np.float32)) and got["batch_verdict.npy"].tolist() == [0.0]
+    pick = got["transcript_sample_proofs.npy"].astype(int)
+    assert pick.size == bench.DUMP_TRANSCRIPTS and len(set(pick.tolist())) == pick.size and pick.max() < v.size
+    lo, hi = got["transcript_sample.npy"][:, 0], got["transcript_sample.npy"][:, 1]
+    assert lo.max() < 2 ** 32 and hi.max() < 2 ** 32
+    i0 = int(pick[0])
+    head = [i0, i0 % 2, 2 + i0 % 3, i0, (1 << 64) - 1, 3]
+    assert [int(h) << 32 | int(x) for x, h in zip(lo[:6], hi[:6])] == head
+
+
+def _main_worker(rank, world, port, q, dump_dir):
+    """One rank of `bench.py --gpus 2` (a plain run) through main() itself on the host: gloo for the
+    per-step exchange and the final reduction, the C restatement of the verifier behind a stand-in
+    for the device batch (the library's Context / Air / Claim / Batch are replaced; nothing else)."""
+    import contextlib
+    import io
+    import json
+    for p in ("oracle", "neptune-core_amd", ""):
+        sys.path.insert(0, os.path.join(ROOT, p))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), RANK=str(rank),
+                      LOCAL_RANK=str(rank), NHIP_FINAL_BACKEND="gloo", NHIP_BENCH_NO_SET_DEVICE="1")
+    import numpy as np
+    import torch
+    import coracle as C
+    import stark_ref as S
+    import neptune_hip as nh
+    import neptune_hip.stark as NS
+    import bench
+
+    torch.cuda.synchronize = lambda *a, **k: None  # no device in this process
+
+    class Ctx:
+        lib = object()
+
+        def __init__(self, dev):
+            pass
+
+        def synchronize(self):
+            pass
+
+        def close(self):
+            pass
+
+    class Batch:
+        KEYS = ("proof_words", "ms_decode", "ms_upload", "tip5_perms_static", "tip5_perms_merkle", "ms_device_decode",
+                "ms_fiat_shamir", "ms_row_hash", "ms_merkle", "ms_merkle_hash", "ms_ood_air", "ms_fri", "ms_deep",
+                "ms_device_total")
+        verdicts = None
+
+        def __init__(self, ctx, air, stark, claims, proofs):
+            self.ctx, self.n = ctx, len(proofs)
+            if Batch.verdicts is None:
+                Batch.verdicts = np.asarray(C.stark_verify_batch(air, S.StarkParams(), claims, proofs, threads=2),
+                                            dtype=np.uint8)
+
+        def set_streams(self, k):
+            return self
+
+        def set_graph(self, on=True):
+            return self
+
+        def launch(self):
+            pass
+
+        def wait(self):
+            return Batch.verdicts.copy(), bool(Batch.verdicts.all())
+
+        def stats(self):
+            return {k: 1.0 for k in self.KEYS}
+
+        def transcript(self, i):
+            return [(i, 0, 0)], [0] * 80, 0
+
+        def close(self):
+            pass
+
+    nh.Context, NS.Batch, NS.Air, NS.Claim = Ctx, Batch, (lambda words: words), (lambda *c: c)
+    sys.argv = ["bench.py", "--gpus", str(world), "--proofs", "12", "--steps", "5", "--warmup", "2",
+                "--air", "synthetic", "--input-form", "canonical", "--dump-outputs", dump_dir]
+    out = io.StringIO()
+    with contextlib.redirect_stdout(out):
+        rc = bench.main()
+    line = out.getvalue().strip()
+    q.put((rank, rc, json.loads(line.splitlines()[-1]) if line else None))
+
+
+def test_main_two_ranks_plain_run_on_the_host(tmp_path):
+    """main() at world size 2 past the timed region: five timed steps with the per-step verdict
+    exchange, the final reduction, rank 0's result line (exit 0 on both ranks, every exchanged verdict
+    vector the expected one, no --full field) and rank 0's dump of its own shard's verdicts."""
+    import numpy as np
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_main_worker, args=(r, 2, port, q, str(tmp_path / "dump"))) for r in range(2)]
+    for p in procs:
+        p.start()
+    import queue
+    res, waited = [], 0
+    while len(res) < len(procs) and waited < 240 and (any(p.is_alive() for p in procs) or not q.empty()):
+        try:
+            res.append(q.get(timeout=2))
+        except queue.Empty:  # a rank that raised leaves nothing: stop once every process has ended
+            waited += 2
+    for p in procs:
+        p.join(timeout=60 if len(res) == len(procs) else 1)
+        if p.is_alive():
+            p.terminate()
+    assert [(r[0], r[1]) for r in sorted(res)] == [(0, 0), (1, 0)]
+    res = sorted(res)
+    line = res[0][2]
+    assert res[1][2] is None and line["n_gpus"] == 2 and line["steps"] == 5 and line["verdicts_correct"] is True
+    assert line["batch_verdict"] is True and line["config"]["proofs_total"] == 12 and line["ms_per_step"] > 0
+    assert not {"roofline", "pcie_inclusive", "group_stream", "cpu_baseline", "valu_issue"} & set(line)
+    v = np.load(tmp_path / "dump" / "verdicts.npy")
+    assert v.dtype == np.float32 and v.size == line["config"]["proofs_rank0"] and bool(v.all())

@@ -95,3 +95,37 @@ def test_config4_shuffled_order(ctx, c4):
     b.close()
     got = NS.verify_batch(ctx, gair, NS.Stark.default(), [(NS.Claim(*claims[i]), proofs[i]) for i in order])
     assert got == [bool(expect[i]) for i in order]
+
+
+def test_dump_outputs_vs_oracle(ctx, c4, tmp_path):
+    """bench.py --dump-outputs on a launched and waited batch (the first 160 proofs of the job, two
+    of them corrupted): verdicts.npy holds the expected verdicts, and every sampled proof's dumped
+    transcript, put back together from its 32-bit halves, is the oracle's (a rejected one: fail != 0)."""
+    import neptune_hip.stark as NS
+    air_words, pool4, claims, proofs, expect, srcs = c4
+    m = 160
+    assert 0 < (~expect[:m]).sum() < m
+    b = NS.Batch(ctx, NS.Air([int(w) for w in air_words]), NS.Stark.default(), [NS.Claim(*c) for c in claims[:m]],
+                 proofs[:m])
+    b.launch()
+    v, ok = b.wait()
+    bench.dump_outputs(str(tmp_path), b, v, ok)
+    b.close()
+    assert np.load(tmp_path / "verdicts.npy").tolist() == [float(x) for x in expect[:m]]
+    assert np.load(tmp_path / "batch_verdict.npy").tolist() == [0.0]
+    pick = np.load(tmp_path / "transcript_sample_proofs.npy").astype(int).tolist()
+    halves = np.load(tmp_path / "transcript_sample.npy")
+    w = [int(lo) | int(hi) << 32 for lo, hi in halves]
+    pos, seen_bad = 0, 0
+    for i in pick:
+        assert w[pos] == i
+        fail, nx = w[pos + 1], w[pos + 2]
+        xs = [tuple(w[pos + 3 + 3 * k:pos + 6 + 3 * k]) for k in range(nx)]
+        idx = w[pos + 3 + 3 * nx:pos + 3 + 3 * nx + 80]
+        pos += 3 + 3 * nx + 80
+        if expect[i]:
+            assert fail == 0 and (xs, idx) == tuple(pool4["transcripts"][srcs[i]]), i
+        else:
+            assert fail != 0, i
+            seen_bad += 1
+    assert pos == len(w) and len(pick) == bench.DUMP_TRANSCRIPTS and seen_bad == 1
