@@ -423,6 +423,17 @@ int nhip_blk_claims(const uint8_t *bytes, size_t n_bytes, const nhip_blk_block *
 /* n little-endian u64 words at byte `offset` (any alignment), reduced mod p: proof words straight
  * into a (pinned) staging buffer. */
 int nhip_le_words(const uint8_t *bytes, size_t n_bytes, uint64_t offset, size_t n, uint64_t *out);
+/* A run of field words inside a byte buffer: byte offset of the first word (any alignment), words. */
+typedef struct {
+    uint64_t offset, len;
+} nhip_span;
+/* The device counterpart of nhip_le_words: out (host, the sum of the spans' len words, spans back to
+ * back in order) = the spans' words gathered and reduced on the GPU (k_wire_words), bit-exact with
+ * nhip_le_words for each span.  bytes is DMA'd as it lies when it is pinned (nhip_host_alloc*,
+ * nhip_host_register), else it goes through the context's pinned staging.  Spans may overlap or
+ * repeat; one that leaves the buffer is NHIP_ERR_ARG. */
+int nhip_le_words_gpu(nhip_ctx *ctx, const uint8_t *bytes, size_t n_bytes, const nhip_span *spans, size_t n,
+                      uint64_t *out);
 
 /* Peer transactions: `TransferTransaction { kernel, proof }` (protocol/peer/transfer_transaction.rs:31-47). */
 enum { NHIP_TX_PROOF_COLLECTION = 0, NHIP_TX_SINGLE_PROOF = 1 };
@@ -481,6 +492,53 @@ int nhip_arena_ingest_txs(nhip_arena *arena, const uint8_t *bytes, size_t n_byte
 int nhip_arena_ingest_blocks(nhip_arena *arena, const uint8_t *bytes, size_t n_bytes, uint32_t pow_tree_height,
                              nhip_proof *proofs, uint32_t *member_of, uint64_t *block_of, size_t proof_cap,
                              size_t *n_proofs, size_t *n_blocks);
+
+/* ---- in-place submission: proofs verified from the wire bytes as they lie -----
+ * The arena path above reads the receive buffer once and writes the pinned arena once before the DMA
+ * reads it: with the receive itself, four host-DRAM passes per proof byte.  Here the receive buffer IS
+ * the pinned memory (nhip_host_alloc_near): the scanners below only find the proofs (no word copied),
+ * the spans' bytes are DMA'd as they lie, and the device gathers them into the batch's aligned word
+ * buffer (two passes).  bincode's Vec<BFieldElement> is already canonical 8-byte little-endian words,
+ * so params->input_form must be NHIP_INPUT_CANONICAL (else NHIP_ERR_ARG); every word is reduced mod p
+ * on the device (BFieldElement::new), so the batch holds the bits the arena path would.
+ *
+ * Scanners (host only, no GPU).  Back-to-back TransferTransactions (transfer_transaction.rs:31-47,
+ * as received in peer_loop.rs:315-323): up to max_txs of them, every proof (a SingleProof's one, a
+ * ProofCollection's in field order) in stream order.  Stops early with NHIP_OK, before the transaction
+ * that does not fit, when span_cap is reached (*consumed < n_bytes: submit, continue from there);
+ * NHIP_ERR_DECODE at a malformed transaction (those before it are counted); NHIP_ERR_ARG when the
+ * first transaction alone needs more than span_cap spans (never NHIP_OK with *consumed == 0 on a
+ * non-empty stream).  *n_txs, *n_proofs, *consumed nullable. */
+int nhip_wire_scan_txs(const uint8_t *bytes, size_t n_bytes, size_t max_txs, nhip_span *spans, size_t span_cap,
+                       size_t *n_txs, size_t *n_proofs, size_t *consumed);
+/* A blk file's bytes (import_blocks_from_files.rs:100-115): the SingleProof block proof of every
+ * block (block_of[i] = its block's index; nullable).  A malformed block fails the whole file
+ * (NHIP_ERR_DECODE, no span returned); NHIP_ERR_ARG when span_cap is short of the file's SingleProof
+ * blocks. */
+int nhip_wire_scan_blocks(const uint8_t *bytes, size_t n_bytes, uint32_t pow_tree_height, nhip_span *spans,
+                          uint64_t *block_of, size_t span_cap, size_t *n_proofs, size_t *n_blocks);
+/* nhip_verify_batch / nhip_batch_prepare / nhip_batch_refill with proof i = spans[i] of bytes[n_bytes]
+ * (a span that leaves the buffer: NHIP_ERR_ARG).  The spans are sorted by offset and neighbours at
+ * most 64 KB apart go as one copy, gap included; pinned bytes are DMA'd straight from the caller's
+ * buffer, other memory is copied byte for byte through the context's pinned staging.  When the call
+ * returns the bytes may be reused (they are on the device). */
+int nhip_verify_batch_wire(nhip_ctx *ctx, nhip_air *air, const nhip_stark_params *params, const nhip_claim *claims,
+                           const uint8_t *bytes, size_t n_bytes, const nhip_span *spans, size_t n, uint8_t *verdicts,
+                           nhip_stats *stats);
+int nhip_batch_prepare_wire(nhip_ctx *ctx, nhip_air *air, const nhip_stark_params *params, const nhip_claim *claims,
+                            const uint8_t *bytes, size_t n_bytes, const nhip_span *spans, size_t n,
+                            nhip_batch **out);
+int nhip_batch_refill_wire(nhip_ctx *ctx, nhip_batch *batch, nhip_air *air, const nhip_stark_params *params,
+                           const nhip_claim *claims, const uint8_t *bytes, size_t n_bytes, const nhip_span *spans,
+                           size_t n);
+/* nhip_group_stream_submit from wire bytes: proof i = spans[i] of bytes[n_bytes], placed on member
+ * member_of[i], or by nhip_group_shard's rule (LPT on the span length) when member_of is NULL.  Each
+ * member uploads its own share's runs.  One receive buffer per socket, allocated with
+ * nhip_host_alloc_near on a member of that socket, keeps the DMA reads node-local; which buffer a
+ * message is received into is the caller's choice.  The stream's params must be NHIP_INPUT_CANONICAL. */
+int nhip_group_stream_submit_wire(nhip_group_stream *stream, const nhip_claim *claims, const uint8_t *bytes,
+                                  size_t n_bytes, const nhip_span *spans, const uint32_t *member_of, size_t n,
+                                  uint8_t *verdicts, uint8_t *all_ok);
 
 /* ---- proof of work (neptune-core/src/protocol/consensus/block/pow.rs) ---
  * PowMastPaths (pow.rs:202-207): MAST authentication paths of the pow field (BlockHeader, 3),

@@ -34,6 +34,7 @@
 //
 // Everything is host code: parsing is byte-serial and a few hundred MB/s per thread is far above
 // what a verifier batch consumes.
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -529,3 +530,79 @@ bool tx_proof_spans(const uint8_t* bytes, size_t n, std::vector<uint64_t>& spans
     return true;
 }
 }  // namespace nhip
+
+// ---- in-place scanners: where the proofs lie in the wire bytes, no word copied
+extern "C" {
+
+int nhip_wire_scan_txs(const uint8_t* bytes, size_t n_bytes, size_t max_txs, nhip_span* spans, size_t span_cap,
+                       size_t* n_txs, size_t* n_proofs, size_t* consumed) {
+    if (n_txs) *n_txs = 0;
+    if (n_proofs) *n_proofs = 0;
+    if (consumed) *consumed = 0;
+    if ((n_bytes && !bytes) || (span_cap && !spans)) return NHIP_ERR_ARG;
+    try {
+        std::vector<uint64_t> sp;
+        size_t pos = 0, txs = 0, placed = 0;
+        int rc = NHIP_OK;
+        while (pos < n_bytes && txs < max_txs) {
+            sp.clear();
+            uint64_t size = 0;
+            if (!nhip::tx_proof_spans(bytes + pos, n_bytes - pos, sp, size)) {
+                rc = NHIP_ERR_DECODE;  // the transactions before it stay counted
+                break;
+            }
+            const size_t np = sp.size() / 2;
+            if (placed + np > span_cap) {
+                // the span array is full: stop before this tx; a first tx that can never fit is the
+                // caller's error, not an empty success to loop on
+                if (txs == 0) rc = NHIP_ERR_ARG;
+                break;
+            }
+            for (size_t i = 0; i < np; ++i) spans[placed + i] = nhip_span{sp[2 * i] + pos, sp[2 * i + 1]};
+            placed += np;
+            pos += size;
+            ++txs;
+        }
+        if (n_txs) *n_txs = txs;
+        if (n_proofs) *n_proofs = placed;
+        if (consumed) *consumed = pos;
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+int nhip_wire_scan_blocks(const uint8_t* bytes, size_t n_bytes, uint32_t pow_tree_height, nhip_span* spans,
+                          uint64_t* block_of, size_t span_cap, size_t* n_proofs, size_t* n_blocks) {
+    if (n_proofs) *n_proofs = 0;
+    if (n_blocks) *n_blocks = 0;
+    if ((n_bytes && !bytes) || (span_cap && !spans)) return NHIP_ERR_ARG;
+    try {
+        size_t nb = 0;
+        int rc = nhip_blk_scan(bytes, n_bytes, pow_tree_height, nullptr, 0, &nb);
+        if (rc) {
+            if (n_blocks) *n_blocks = nb;
+            return rc;  // a malformed block fails the whole file (import_blocks_from_files.rs:100-115)
+        }
+        std::vector<nhip_blk_block> blocks(std::max<size_t>(nb, 1));
+        rc = nhip_blk_scan(bytes, n_bytes, pow_tree_height, blocks.data(), nb, &nb);
+        if (rc) return rc;
+        size_t singles = 0;
+        for (size_t b = 0; b < nb; ++b) singles += blocks[b].proof_kind == NHIP_BLOCK_PROOF_SINGLE ? 1 : 0;
+        if (singles > span_cap) return NHIP_ERR_ARG;
+        size_t placed = 0;
+        for (size_t b = 0; b < nb; ++b)
+            if (blocks[b].proof_kind == NHIP_BLOCK_PROOF_SINGLE) {
+                spans[placed] = nhip_span{blocks[b].proof_offset, blocks[b].proof_len};
+                if (block_of) block_of[placed] = b;
+                ++placed;
+            }
+        if (n_proofs) *n_proofs = placed;
+        if (n_blocks) *n_blocks = nb;
+        return NHIP_OK;
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 #include "device_scope.hpp"
 #include "host_numa.hpp"
 #include "kernels.hpp"
+#include "wire.hpp"
 
 struct nhip_ctx {
     int device = 0;
@@ -147,7 +148,9 @@ extern "C" {
 // 2300: nhip_air_create_ex (compiler options instead of environment variables), nhip_set_climb_from_ops,
 // the per-member proof arenas (nhip_arena_*, nhip_group_stream_submit_placed), nhip_queue_latencies,
 // nhip_batch_set_graph
-int nhip_abi_version(void) { return 2300; }
+// 2400: the in-place feed path (nhip_span, nhip_le_words_gpu, nhip_wire_scan_*, nhip_verify_batch_wire,
+// nhip_batch_prepare_wire, nhip_batch_refill_wire, nhip_group_stream_submit_wire)
+int nhip_abi_version(void) { return 2400; }
 
 int nhip_set_fs_form(int form) { return nhip::set_fs_form(form) == 0 ? NHIP_OK : NHIP_ERR_ARG; }
 int nhip_set_climb_from_ops(int64_t ops) { return nhip::set_climb_from_ops(ops) == 0 ? NHIP_OK : NHIP_ERR_ARG; }
@@ -489,6 +492,68 @@ int nhip_mtree_verify(nhip_ctx* c, const uint64_t* roots, size_t n_roots, const 
     e = hipMemcpyAsync(v, p[4], n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     return hip_fail(e);
+}
+
+// ------------------------------------------------------------------ wire bytes -> words
+int nhip_internal_is_pinned(const void* p, size_t bytes);  // stark_host.cpp
+
+// The device counterpart of nhip_le_words: the spans' raw bytes uploaded run by run (wire.hpp), gathered
+// by k_wire_words into one aligned word buffer (span i at the sum of the lengths before it), read back.
+int nhip_le_words_gpu(nhip_ctx* c, const uint8_t* bytes, size_t n_bytes, const nhip_span* spans, size_t n,
+                      uint64_t* out) {
+    if (!c || (n_bytes && !bytes) || (n && !spans) || n > 0xFFFFFFFFull) return NHIP_ERR_ARG;
+    if (!nhip::wire_spans_ok(spans, n, n_bytes)) return NHIP_ERR_ARG;
+    try {
+        std::vector<nhip::ProofIn> in(n);
+        uint64_t total = 0;
+        for (size_t i = 0; i < n; ++i) {
+            in[i] = nhip::ProofIn{};
+            in[i].off = total;
+            in[i].len = spans[i].len;
+            total += spans[i].len;
+        }
+        if (total == 0) return NHIP_OK;
+        if (!out) return NHIP_ERR_ARG;
+        nhip::WirePlan plan;
+        nhip::wire_plan(bytes, spans, n, plan);
+        std::lock_guard<std::mutex> g(c->mu);
+        const DeviceScope device_scope(c->device);
+        size_t sizes[4] = {plan.raw_bytes, n * 8, n * sizeof(nhip::ProofIn), (size_t)total * 8};
+        void* p[4];
+        int rc = carve(c, sizes, p);
+        if (rc) return rc;
+        bool any_pageable = false;
+        for (const nhip::WireRun& r : plan.runs)
+            any_pageable |= !nhip_internal_is_pinned(bytes + r.start, (size_t)(r.end - r.start));
+        std::vector<uint8_t> pageable;
+        uint8_t* stage = nullptr;
+        if (any_pageable) {
+            stage = (uint8_t*)nhip_internal_staging(c, plan.raw_bytes);
+            if (!stage) {
+                pageable.resize(plan.raw_bytes);
+                stage = pageable.data();
+            }
+        }
+        hipError_t e = nhip::wire_upload(plan, bytes, (uint8_t*)p[0], stage,
+                                         [](const void* q, size_t b) { return nhip_internal_is_pinned(q, b) != 0; },
+                                         c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(p[1], plan.boff.data(), sizes[1], hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(p[2], in.data(), sizes[2], hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);  // the sources are this call's
+            return hip_fail(e);
+        }
+        rc = timed_launch(c, [&] {
+            return nhip::launch_wire_words((const uint8_t*)p[0], (const uint64_t*)p[1], (const nhip::ProofIn*)p[2],
+                                           (uint32_t)n, total, (uint64_t*)p[3], c->stream);
+        });
+        if (rc == NHIP_OK) e = hipMemcpyAsync(out, p[3], sizes[3], hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        if (rc) return rc;
+        return hip_fail(e != hipSuccess ? e : es);
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
 }
 
 // ------------------------------------------------------------------ timing

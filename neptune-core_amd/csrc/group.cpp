@@ -231,6 +231,7 @@ struct MemberSlots {
     bool in_flight[2] = {false, false};
     std::vector<nhip_claim> claims;
     std::vector<nhip_proof> proofs;
+    std::vector<nhip_span> spans;  // a wire submit's share (nhip_group_stream_submit_wire)
     std::vector<uint8_t> v[2];  // per slot: sized to that slot's share when the slot is refilled
 };
 
@@ -341,10 +342,18 @@ int nhip_group_stream_create(nhip_group* g, nhip_air* air, const nhip_stark_para
     return NHIP_OK;
 }
 
-static int stream_submit(nhip_group_stream* st, const nhip_claim* claims, const nhip_proof* proofs,
-                         const uint32_t* placed, size_t n, uint8_t* verdicts, uint8_t* all_ok) {
+// The batch's proofs are nhip_proof records (`proofs`), or spans of wire bytes (`spans` of
+// bytes[n_bytes] when `wire`: each member uploads its share's runs and gathers them on its GPU).
+static int stream_submit(nhip_group_stream* st, const nhip_claim* claims, const nhip_proof* proofs, bool wire,
+                         const uint8_t* bytes, size_t n_bytes, const nhip_span* spans, const uint32_t* placed,
+                         size_t n, uint8_t* verdicts, uint8_t* all_ok) {
     if (!st) return NHIP_ERR_ARG;
-    if (n && (!claims || !proofs || !verdicts)) return NHIP_ERR_ARG;
+    if (n && (!claims || (wire ? !spans : !proofs) || !verdicts)) return NHIP_ERR_ARG;
+    if (wire) {  // a wire submit's own argument checks, before any member is touched
+        if (st->params.input_form != NHIP_INPUT_CANONICAL || (n_bytes && !bytes)) return NHIP_ERR_ARG;
+        for (size_t i = 0; i < n; ++i)
+            if (spans[i].offset > n_bytes || spans[i].len > (n_bytes - spans[i].offset) / 8) return NHIP_ERR_ARG;
+    }
     const size_t M = st->m.size();
     if (placed)
         for (size_t i = 0; i < n; ++i)
@@ -358,7 +367,12 @@ static int stream_submit(nhip_group_stream* st, const nhip_claim* claims, const 
         std::vector<uint32_t> member_of(n);
         int rc = NHIP_OK;
         if (placed) std::copy(placed, placed + n, member_of.begin());  // the caller's placement (arenas)
-        else rc = nhip_group_shard(proofs, n, M, member_of.data());
+        else if (!wire) rc = nhip_group_shard(proofs, n, M, member_of.data());
+        else {  // the same rule on the span lengths
+            std::vector<nhip_proof> lens(n);
+            for (size_t i = 0; i < n; ++i) lens[i] = nhip_proof{nullptr, (size_t)spans[i].len};
+            rc = nhip_group_shard(lens.data(), n, M, member_of.data());
+        }
         if (rc) return rc;
         for (auto& v : B.idx) v.clear();
         for (size_t i = 0; i < n; ++i) B.idx[member_of[i]].push_back(i);
@@ -367,9 +381,11 @@ static int stream_submit(nhip_group_stream* st, const nhip_claim* claims, const 
             MemberSlots& ms = st->m[mm];
             ms.claims.clear();
             ms.proofs.clear();
+            ms.spans.clear();
             for (size_t i : B.idx[mm]) {
                 ms.claims.push_back(claims[i]);
-                ms.proofs.push_back(proofs[i]);
+                if (!wire) ms.proofs.push_back(proofs[i]);
+                else ms.spans.push_back(spans[i]);
             }
             // slot s is idle (its batch k - 2 was completed by the previous submit): size its verdict
             // buffer to THIS share, the one complete_member(mm, s) will read back (here, on the
@@ -384,10 +400,17 @@ static int stream_submit(nhip_group_stream* st, const nhip_claim* claims, const 
             const size_t cnt = B.idx[mm].size();
             if (cnt) {
                 // slot s is idle: its batch (k - 2) was completed by the previous submit
-                int r = ms.b[s] ? nhip_batch_refill(c, ms.b[s], st->air, &st->params, ms.claims.data(),
+                int r;
+                if (!wire)
+                    r = ms.b[s] ? nhip_batch_refill(c, ms.b[s], st->air, &st->params, ms.claims.data(),
                                                     ms.proofs.data(), cnt)
                                 : nhip_batch_prepare(c, st->air, &st->params, ms.claims.data(), ms.proofs.data(),
                                                      cnt, &ms.b[s]);
+                else
+                    r = ms.b[s] ? nhip_batch_refill_wire(c, ms.b[s], st->air, &st->params, ms.claims.data(), bytes,
+                                                         n_bytes, ms.spans.data(), cnt)
+                                : nhip_batch_prepare_wire(c, st->air, &st->params, ms.claims.data(), bytes, n_bytes,
+                                                          ms.spans.data(), cnt, &ms.b[s]);
                 if (!r) {
                     nhip_stats bs{};
                     nhip_batch_stats(ms.b[s], &bs);
@@ -419,13 +442,19 @@ static int stream_submit(nhip_group_stream* st, const nhip_claim* claims, const 
 
 int nhip_group_stream_submit(nhip_group_stream* st, const nhip_claim* claims, const nhip_proof* proofs, size_t n,
                              uint8_t* verdicts, uint8_t* all_ok) {
-    return stream_submit(st, claims, proofs, nullptr, n, verdicts, all_ok);
+    return stream_submit(st, claims, proofs, false, nullptr, 0, nullptr, nullptr, n, verdicts, all_ok);
 }
 
 int nhip_group_stream_submit_placed(nhip_group_stream* st, const nhip_claim* claims, const nhip_proof* proofs,
                                     const uint32_t* member_of, size_t n, uint8_t* verdicts, uint8_t* all_ok) {
     if (n && !member_of) return NHIP_ERR_ARG;
-    return stream_submit(st, claims, proofs, member_of, n, verdicts, all_ok);
+    return stream_submit(st, claims, proofs, false, nullptr, 0, nullptr, member_of, n, verdicts, all_ok);
+}
+
+int nhip_group_stream_submit_wire(nhip_group_stream* st, const nhip_claim* claims, const uint8_t* bytes,
+                                  size_t n_bytes, const nhip_span* spans, const uint32_t* member_of, size_t n,
+                                  uint8_t* verdicts, uint8_t* all_ok) {
+    return stream_submit(st, claims, nullptr, true, bytes, n_bytes, spans, member_of, n, verdicts, all_ok);
 }
 
 int nhip_group_stream_finish(nhip_group_stream* st) {

@@ -103,6 +103,15 @@ struct ProofIn {
     uint32_t sized_log2_ph, pad;
 };
 
+// ---- wire bytes -> aligned words (wire_kernels.hip): words[in[i].off + k] = the little-endian u64 at
+// d_raw + d_boff[i] + 8k, reduced mod p, for k < in[i].len; the proofs' words lie back to back from
+// word 0 in `in` order (total_words of them).  The kernel's aligned loads reach at most 15 bytes
+// below a proof's first byte and 16 bytes past its last: d_raw sits in an allocation whose base is
+// 16-byte aligned and which extends WIRE_TAIL_PAD bytes past the last proof byte.
+static constexpr size_t WIRE_TAIL_PAD = 16;
+hipError_t launch_wire_words(const uint8_t* d_raw, const uint64_t* d_boff, const ProofIn* d_in, uint32_t n,
+                             uint64_t total_words, uint64_t* d_words, hipStream_t st);
+
 // Merkle hash launches (k_mp_hash / k_mp_hash_wide) timed per launch (start / stop event pairs)
 static constexpr uint32_t MAX_HASH_LAUNCHES = 64;
 

@@ -30,6 +30,7 @@
 #include "goldilocks.hpp"
 #include "kernels.hpp"
 #include "stark.hpp"
+#include "wire.hpp"
 
 using namespace nhip;
 
@@ -51,6 +52,13 @@ struct HostBatch {
     uint32_t max_R = 0, max_last_cw = 1, levels = 0;
     uint32_t fs_stride = 0, xs_stride = 0;
     uint64_t perms_static = 0, perms_lcw = 0;  // device-counted, per run
+};
+
+// A batch's proofs given as spans of a wire buffer (the in-place feed path) instead of nhip_proof records.
+struct WireSrc {
+    const uint8_t* bytes;
+    size_t n_bytes;
+    const nhip_span* spans;
 };
 
 uint64_t claim_words(const nhip_claim& c) { return (uint64_t)c.output_len + c.input_len + 10; }
@@ -157,6 +165,8 @@ struct VerifyScratch {
     size_t dmem_bytes = 0;
     void* dwords = nullptr;  // proof words (uploaded while they are decoded)
     size_t dwords_bytes = 0;
+    void* draw = nullptr;  // raw wire bytes of an in-place batch (k_wire_words gathers them into dwords)
+    size_t draw_bytes = 0;
     hipStream_t main = nullptr, aux = nullptr;
     hipEvent_t ev[STARK_EVENTS] = {};
     bool streams = false;
@@ -176,6 +186,7 @@ static void free_verify_scratch(void* p) {
     if (sc->h_out) (void)hipHostFree(sc->h_out);
     if (sc->dmem) (void)hipFree(sc->dmem);
     if (sc->dwords) (void)hipFree(sc->dwords);
+    if (sc->draw) (void)hipFree(sc->draw);
     delete sc;
 }
 
@@ -194,6 +205,8 @@ struct nhip_batch {
     size_t dmem_bytes = 0, h_out_bytes = 0;  // owned allocations (refill reuses them when they fit)
     void* dwords = nullptr;                  // proof words (owned unless borrowed from the scratch)
     size_t dwords_bytes = 0;
+    void* draw = nullptr;                    // raw wire bytes of an in-place fill (owned / borrowed as dwords)
+    size_t draw_bytes = 0;
     bool timed = false, in_flight = false;
     struct {
         double decode, fs, rows, plan, hash, roots, ood, fri, deep, total;
@@ -657,17 +670,27 @@ namespace {
 // scratch sized from the padded height each proof header declares.  reuse == nullptr: a new batch
 // (*out); otherwise `reuse` is refilled in place (same streams and events; its device memory reused
 // when large enough).
+// The proofs come from one of two sources: nhip_proof records (word pointers, `proofs`), or spans of a
+// wire buffer (`wire`, the in-place path of DESIGN.md §6b: the spans' raw bytes are uploaded as they lie
+// and k_wire_words gathers them into the word buffer on the device; canonical input form only).
 int batch_prepare(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, const nhip_claim* claims,
-                  const nhip_proof* proofs, size_t n, nhip_batch** out, VerifyScratch* scr,
+                  const nhip_proof* proofs, const WireSrc* wire, size_t n, nhip_batch** out, VerifyScratch* scr,
                   nhip_batch* reuse = nullptr) {
-    if (!ctx || !out || (n && (!claims || !proofs))) return NHIP_ERR_ARG;
+    // the wire source's own argument checks come first: they need no device
+    if (wire) {
+        if (proofs || !sp || sp->input_form != NHIP_INPUT_CANONICAL) return NHIP_ERR_ARG;
+        if ((wire->n_bytes && !wire->bytes) || (n && !wire->spans)) return NHIP_ERR_ARG;
+        if (!wire_spans_ok(wire->spans, n, wire->n_bytes)) return NHIP_ERR_ARG;
+    }
+    if (!ctx || !out || (n && (!claims || (!proofs && !wire)))) return NHIP_ERR_ARG;
     if (reuse && (reuse->in_flight || reuse->scratch)) return NHIP_ERR_ARG;
     if (!reuse) *out = nullptr;
     Dims D{};
     if (!dims_from(sp, air, D)) return NHIP_ERR_ARG;
     if (n > 0xFFFFFFFFull) return NHIP_ERR_ARG;
+    auto proof_len = [&](size_t i) -> uint64_t { return wire ? wire->spans[i].len : (uint64_t)proofs[i].len; };
     for (size_t i = 0; i < n; ++i)
-        if ((proofs[i].len && !proofs[i].words) || (claims[i].input_len && !claims[i].input) ||
+        if ((!wire && proofs[i].len && !proofs[i].words) || (claims[i].input_len && !claims[i].input) ||
             (claims[i].output_len && !claims[i].output) || claims[i].input_len > 0xFFFFFFFFull ||
             claims[i].output_len > 0xFFFFFFFFull)
             return NHIP_ERR_ARG;
@@ -680,6 +703,7 @@ int batch_prepare(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, con
         if (!reuse) {
             if (!scr && b->dmem) (void)hipFree(b->dmem);
             if (!scr && b->dwords) (void)hipFree(b->dwords);
+            if (!scr && b->draw) (void)hipFree(b->draw);
             delete b;
         } else {
             b->H = HostBatch{};
@@ -707,8 +731,8 @@ int batch_prepare(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, con
         uint64_t cur = 0;
         for (size_t i = 0; i < n; ++i) {
             pin[i].off = cur;
-            pin[i].len = proofs[i].len;
-            cur += proofs[i].len;
+            pin[i].len = proof_len(i);
+            cur += proof_len(i);
         }
         H.proof_words = cur;
         for (size_t i = 0; i < n; ++i) {
@@ -721,8 +745,17 @@ int batch_prepare(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, con
         for (size_t i = 0; i < n; ++i) {
             uint64_t lph = 0;
             ProofShape s{};
-            const bool hdr = D.mont_words ? header_log2_ph<true>(proofs[i].words, proofs[i].len, lph)
-                                          : header_log2_ph<false>(proofs[i].words, proofs[i].len, lph);
+            bool hdr;
+            if (wire) {
+                // the five header words by an unaligned-safe load: the wire pointer is never a uint64_t*
+                uint64_t h5[5];
+                const uint64_t len = proof_len(i);
+                if (len >= 5) std::memcpy(h5, wire->bytes + wire->spans[i].offset, sizeof(h5));
+                hdr = len >= 5 && header_log2_ph<false>(h5, len, lph);
+            } else {
+                hdr = D.mont_words ? header_log2_ph<true>(proofs[i].words, proofs[i].len, lph)
+                                   : header_log2_ph<false>(proofs[i].words, proofs[i].len, lph);
+            }
             if (hdr && shape_of(D, lph, s)) {
                 pin[i].sized_log2_ph = s.log2_ph;
                 shp[i] = s;
@@ -766,7 +799,52 @@ int batch_prepare(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, con
         // pinned staging (same layout as the device buffer) by host threads, ~64 MB chunks in proof
         // order, each chunk's DMA issued as soon as its copies are done.  The claim encodings go
         // through the staging too.
-        {
+        std::vector<uint64_t> wire_boff;  // wire source: each proof's first byte in the device raw buffer
+        if (wire) {
+            // ---- wire source: the spans' raw bytes, run by run (wire.hpp), into the batch's device raw
+            // buffer (grow-only, beside the word buffer; the scratch's when borrowed); k_wire_words turns
+            // them into the proof region of the word buffer once the ProofIn records are up (below).
+            // The claim encodings are staged as for the other source, the raw bytes of a pageable
+            // buffer after them.
+            WirePlan plan;
+            wire_plan(wire->bytes, wire->spans, n, plan);
+            void** dr = scr ? &scr->draw : &b->draw;
+            size_t* drb = scr ? &scr->draw_bytes : &b->draw_bytes;
+            if (*drb < plan.raw_bytes) {
+                const size_t have = *drb;
+                if (*dr) (void)hipFree(*dr);
+                *dr = nullptr;
+                *drb = 0;
+                const size_t want = grown(plan.raw_bytes, have, reuse || scr);
+                const hipError_t ea = hipMalloc(dr, want);
+                if (ea != hipSuccess) {
+                    if (scr) b->dwords = nullptr, b->draw = nullptr;
+                    return fail_out(hipfail(ea));
+                }
+                *drb = want;
+            }
+            b->draw = *dr;
+            const uint64_t cw = H.words_total - H.proof_words;  // claim words
+            const size_t raw_at = (size_t)((cw * 8 + 8 + 63) & ~(uint64_t)63);
+            bool any_pageable = false;
+            for (const WireRun& r : plan.runs)
+                any_pageable |= !pinned().contains(wire->bytes + r.start, (size_t)(r.end - r.start));
+            const size_t sbytes = raw_at + (any_pageable ? plan.raw_bytes : 0);
+            std::vector<uint64_t> pageable;
+            uint8_t* stage = (uint8_t*)nhip_internal_staging(ctx, sbytes);
+            if (!stage) {
+                pageable.resize(sbytes / 8 + 1);
+                stage = (uint8_t*)pageable.data();
+            }
+            e = wire_upload(plan, wire->bytes, (uint8_t*)b->draw, stage + raw_at,
+                            [](const void* p, size_t bytes) { return pinned().contains(p, bytes); }, st);
+            uint64_t* cstage = (uint64_t*)stage;
+            for (size_t i = 0; i < n; ++i)
+                encode_claim(claims[i], false, cstage + (pin[i].claim_off - H.proof_words));
+            dma(H.proof_words, cstage, cw);
+            if (stage == (uint8_t*)pageable.data() && e == hipSuccess) e = hipStreamSynchronize(st);
+            wire_boff.swap(plan.boff);
+        } else {
             std::vector<uint8_t> direct(n, 0);
             for (size_t i = 0; i < n; ++i)
                 direct[i] = proofs[i].len && pinned().contains(proofs[i].words, proofs[i].len * 8) ? 1 : 0;
@@ -924,7 +1002,7 @@ int batch_prepare(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, con
                              // plan counters | verdicts], so one memset clears the counters and one
                              // copy brings everything back (three fewer dependent packets per batch)
                              OUT_HDR + (size_t)levels * MP_SHARDS * 4 + N1 + 8,
-                             0,
+                             wire ? N1 * 8 : 0,  // wire source: the proofs' byte offsets in the raw buffer
                              mp_total * 16 + 16,
                              mp_total * 40 + 40,
                              (size_t)levels * MP_SHARDS * 8 + 8,
@@ -980,6 +1058,14 @@ int batch_prepare(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, con
             e = hipMemcpyAsync(ptr[13], mp_sbase.data(), mp_sbase.size() * 8, hipMemcpyHostToDevice, st);
         if (e == hipSuccess && levels)
             e = hipMemcpyAsync(ptr[14], mp_scap.data(), mp_scap.size() * 8, hipMemcpyHostToDevice, st);
+        if (wire && n) {
+            // the gather: after the raw uploads and the ProofIn records on this stream, before anything
+            // reads the proof words (the launch streams start after the synchronize below)
+            if (e == hipSuccess) e = hipMemcpyAsync(ptr[10], wire_boff.data(), n * 8, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess)
+                e = launch_wire_words((const uint8_t*)b->draw, (const uint64_t*)ptr[10], (const ProofIn*)ptr[8],
+                                      (uint32_t)n, H.proof_words, d_words, st);
+        }
         {
             const hipError_t es = hipStreamSynchronize(st);  // the sources are host vectors / the staging
             if (e == hipSuccess) e = es;
@@ -1064,12 +1150,13 @@ static int launch_resources(nhip_batch* b);
 static void drop_graph(nhip_batch* b);
 
 static int prepare_resident(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, const nhip_claim* claims,
-                            const nhip_proof* proofs, size_t n, nhip_batch** out, nhip_batch* reuse) {
+                            const nhip_proof* proofs, const WireSrc* wire, size_t n, nhip_batch** out,
+                            nhip_batch* reuse) {
     if (reuse && !reuse->in_flight) {  // new contents: the captured launch sequence is stale
         const DeviceScope device_scope(reuse->device);
         drop_graph(reuse);
     }
-    const int rc = batch_prepare(ctx, air, sp, claims, proofs, n, out, nullptr, reuse);
+    const int rc = batch_prepare(ctx, air, sp, claims, proofs, wire, n, out, nullptr, reuse);
     if (rc != NHIP_OK || !*out) return rc;
     std::lock_guard<std::mutex> g(*nhip_internal_mutex(ctx));
     const DeviceScope device_scope((*out)->device);
@@ -1079,14 +1166,29 @@ static int prepare_resident(nhip_ctx* ctx, nhip_air* air, const nhip_stark_param
 
 int nhip_batch_prepare(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, const nhip_claim* claims,
                        const nhip_proof* proofs, size_t n, nhip_batch** out) {
-    NHIP_GUARD(prepare_resident(ctx, air, sp, claims, proofs, n, out, nullptr))
+    NHIP_GUARD(prepare_resident(ctx, air, sp, claims, proofs, nullptr, n, out, nullptr))
+}
+
+int nhip_batch_prepare_wire(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, const nhip_claim* claims,
+                            const uint8_t* bytes, size_t n_bytes, const nhip_span* spans, size_t n, nhip_batch** out) {
+    const WireSrc wire{bytes, n_bytes, spans};
+    NHIP_GUARD(prepare_resident(ctx, air, sp, claims, nullptr, &wire, n, out, nullptr))
 }
 
 int nhip_batch_refill(nhip_ctx* ctx, nhip_batch* b, nhip_air* air, const nhip_stark_params* sp,
                       const nhip_claim* claims, const nhip_proof* proofs, size_t n) {
     if (!b) return NHIP_ERR_ARG;
     nhip_batch* out = b;
-    NHIP_GUARD(prepare_resident(ctx, air, sp, claims, proofs, n, &out, b))
+    NHIP_GUARD(prepare_resident(ctx, air, sp, claims, proofs, nullptr, n, &out, b))
+}
+
+int nhip_batch_refill_wire(nhip_ctx* ctx, nhip_batch* b, nhip_air* air, const nhip_stark_params* sp,
+                           const nhip_claim* claims, const uint8_t* bytes, size_t n_bytes, const nhip_span* spans,
+                           size_t n) {
+    if (!b) return NHIP_ERR_ARG;
+    nhip_batch* out = b;
+    const WireSrc wire{bytes, n_bytes, spans};
+    NHIP_GUARD(prepare_resident(ctx, air, sp, claims, nullptr, &wire, n, &out, b))
 }
 
 // The batch's launch resources: its two streams and timing events (or a verify scratch's) and the
@@ -1456,6 +1558,7 @@ void nhip_batch_destroy(nhip_batch* b) {
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->dmem) (void)hipFree(b->dmem);
     if (b->dwords) (void)hipFree(b->dwords);
+    if (b->draw) (void)hipFree(b->draw);
     delete b;
 }
 
@@ -1528,8 +1631,9 @@ int nhip_host_unregister(void* p) {
     return hipfail(hipHostUnregister(p));
 }
 
-int nhip_verify_batch(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, const nhip_claim* claims,
-                      const nhip_proof* proofs, size_t n, uint8_t* verdicts, nhip_stats* stats) {
+static int verify_batch_from(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, const nhip_claim* claims,
+                             const nhip_proof* proofs, const WireSrc* wire, size_t n, uint8_t* verdicts,
+                             nhip_stats* stats) {
     if (!verdicts && n) return NHIP_ERR_ARG;
     if (!ctx) return NHIP_ERR_ARG;
     auto* scr = (VerifyScratch*)nhip_internal_verify_scratch(
@@ -1539,7 +1643,7 @@ int nhip_verify_batch(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp,
     nhip_batch* b = nullptr;
     int rc;
     try {
-        rc = batch_prepare(ctx, air, sp, claims, proofs, n, &b, scr);
+        rc = batch_prepare(ctx, air, sp, claims, proofs, wire, n, &b, scr);
     } catch (const std::bad_alloc&) {
         return NHIP_ERR_OOM;
     }
@@ -1549,5 +1653,20 @@ int nhip_verify_batch(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp,
     nhip_batch_destroy(b);
     return rc;
 }
+
+int nhip_verify_batch(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, const nhip_claim* claims,
+                      const nhip_proof* proofs, size_t n, uint8_t* verdicts, nhip_stats* stats) {
+    return verify_batch_from(ctx, air, sp, claims, proofs, nullptr, n, verdicts, stats);
+}
+
+int nhip_verify_batch_wire(nhip_ctx* ctx, nhip_air* air, const nhip_stark_params* sp, const nhip_claim* claims,
+                           const uint8_t* bytes, size_t n_bytes, const nhip_span* spans, size_t n, uint8_t* verdicts,
+                           nhip_stats* stats) {
+    const WireSrc wire{bytes, n_bytes, spans};
+    return verify_batch_from(ctx, air, sp, claims, nullptr, &wire, n, verdicts, stats);
+}
+
+// capi.hip (nhip_le_words_gpu): is the range pinned host memory this library knows of?
+int nhip_internal_is_pinned(const void* p, size_t bytes) { return pinned().contains(p, bytes) ? 1 : 0; }
 
 }  // extern "C"

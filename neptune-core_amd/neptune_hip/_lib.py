@@ -90,6 +90,11 @@ class Tx(ctypes.Structure):
                 ("n_merge_path", ctypes.c_uint32), ("n_digests", ctypes.c_uint32), ("seq_words", ctypes.c_uint64)]
 
 
+class Span(ctypes.Structure):
+    """nhip_span: byte offset of a run of field words inside a byte buffer, and its length in words."""
+    _fields_ = [("offset", ctypes.c_uint64), ("len", ctypes.c_uint64)]
+
+
 _pp = ctypes.POINTER(ctypes.c_void_p)
 
 # (name, argtypes) for every symbol of include/neptune_hip.h
@@ -213,6 +218,19 @@ SIGNATURES = {
     "nhip_blk_sequences": ([_vp, _sz, ctypes.c_uint32, ctypes.POINTER(BlkBlock), _vp, _sz, _vp], ctypes.c_int),
     "nhip_blk_claims": ([_vp, _sz, ctypes.POINTER(BlkBlock), _vp, _vp], ctypes.c_int),
     "nhip_le_words": ([_vp, _sz, ctypes.c_uint64, _sz, _vp], ctypes.c_int),
+    "nhip_le_words_gpu": ([_vp, _vp, _sz, ctypes.POINTER(Span), _sz, _vp], ctypes.c_int),
+    "nhip_wire_scan_txs": ([_vp, _sz, _sz, ctypes.POINTER(Span), _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz),
+                            ctypes.POINTER(_sz)], ctypes.c_int),
+    "nhip_wire_scan_blocks": ([_vp, _sz, ctypes.c_uint32, ctypes.POINTER(Span), _vp, _sz, ctypes.POINTER(_sz),
+                               ctypes.POINTER(_sz)], ctypes.c_int),
+    "nhip_verify_batch_wire": ([_vp, _vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), _vp, _sz,
+                                ctypes.POINTER(Span), _sz, _u8p, ctypes.POINTER(Stats)], ctypes.c_int),
+    "nhip_batch_prepare_wire": ([_vp, _vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), _vp, _sz,
+                                 ctypes.POINTER(Span), _sz, _pp], ctypes.c_int),
+    "nhip_batch_refill_wire": ([_vp, _vp, _vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), _vp, _sz,
+                                ctypes.POINTER(Span), _sz], ctypes.c_int),
+    "nhip_group_stream_submit_wire": ([_vp, ctypes.POINTER(Claim), _vp, _sz, ctypes.POINTER(Span), _vp, _sz, _vp,
+                                       _vp], ctypes.c_int),
     "nhip_tx_scan": ([_vp, _sz, ctypes.POINTER(Tx)], ctypes.c_int),
     "nhip_tx_parts": ([_vp, _sz, ctypes.POINTER(Tx), _vp, _vp, _vp, _vp], ctypes.c_int),
     "nhip_timing_enable": ([_vp, ctypes.c_int], ctypes.c_int),

@@ -173,6 +173,129 @@ def marshal(claims: Sequence[Claim], proofs: Sequence[Sequence[int]]):
     return _Marshal(claims, proofs)
 
 
+def _claims_only(claims) -> "_Marshal":
+    return claims if isinstance(claims, _Marshal) else _Marshal(claims, [()] * len(claims))
+
+
+def _wire_source(data):
+    """(address, byte count, keep-alive) of a wire source: a WireBuffer (all of it), or any object with
+    the buffer protocol (bytes, bytearray, memoryview, a uint8 numpy array or a view into one)."""
+    if isinstance(data, WireBuffer):
+        return data.ptr, data.nbytes, data
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    if a.dtype != np.uint8 or a.ndim != 1 or (a.size and not a.flags["C_CONTIGUOUS"]):
+        raise ValueError("wire bytes must be a contiguous one-dimensional uint8 buffer")
+    return (a.ctypes.data if a.size else None), int(a.size), a
+
+
+def _span_array(spans):
+    if isinstance(spans, ctypes.Array) and spans._type_ is _lib.Span:  # a scanner's own array (raw=True)
+        return spans, len(spans)
+    sp = [(int(o), int(n)) for o, n in spans]
+    arr = (_lib.Span * max(len(sp), 1))()
+    for i, (o, n) in enumerate(sp):
+        arr[i].offset, arr[i].len = o, n
+    return arr, len(sp)
+
+
+def wire_scan_txs(data, max_txs: int = None, span_cap: int = None, start: int = 0, raw: bool = False):
+    """nhip_wire_scan_txs over data[start:]: back-to-back TransferTransactions -> (spans, transactions
+    taken, bytes consumed); spans are (byte offset in `data`, words) per proof in stream order.  Host
+    only, no word copied.  Stops before the transaction that would exceed span_cap (continue from
+    start + consumed); ValueError at a malformed transaction.  raw=True: the spans as the C array the
+    scanner filled (offsets from data[start], so submit data[start:]), for a receive loop that hands
+    them straight to from_wire / submit_wire."""
+    addr, n, keep = _wire_source(data)
+    if start > n:
+        raise ValueError("start past the end of the buffer")
+    n -= start
+    cap = span_cap if span_cap is not None else max(1, n // 8)
+    arr = (_lib.Span * max(cap, 1))()
+    nt, npf, used = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    rc = _lib.load().nhip_wire_scan_txs((addr or 0) + start if n else None, n, max_txs if max_txs is not None else n,
+                                        arr, cap, ctypes.byref(nt), ctypes.byref(npf), ctypes.byref(used))
+    if rc == _lib.NHIP_ERR_DECODE:
+        raise ValueError(f"malformed TransferTransaction after {nt.value} transactions ({used.value} bytes)")
+    check(rc, "nhip_wire_scan_txs")
+    if raw:
+        return (_lib.Span * npf.value).from_buffer(arr), nt.value, used.value
+    return [(int(arr[i].offset) + start, int(arr[i].len)) for i in range(npf.value)], nt.value, used.value
+
+
+def wire_scan_blocks(data, pow_tree_height: int):
+    """nhip_wire_scan_blocks: a blk file's bytes -> (spans of the SingleProof block proofs, block index of
+    each).  Host only; a malformed block fails the whole file (NhipError)."""
+    addr, n, keep = _wire_source(data)
+    lib = _lib.load()
+    cnt = ctypes.c_size_t()
+    check(lib.nhip_blk_scan(addr, n, pow_tree_height, None, 0, ctypes.byref(cnt)), "nhip_blk_scan")
+    cap = max(cnt.value, 1)
+    arr = (_lib.Span * cap)()
+    block_of = np.zeros(cap, dtype=np.uint64)
+    npf, nb = ctypes.c_size_t(), ctypes.c_size_t()
+    check(lib.nhip_wire_scan_blocks(addr, n, pow_tree_height, arr, block_of.ctypes.data, cap, ctypes.byref(npf),
+                                    ctypes.byref(nb)), "nhip_wire_scan_blocks")
+    return [(int(arr[i].offset), int(arr[i].len)) for i in range(npf.value)], [int(x) for x in block_of[:npf.value]]
+
+
+class WireBuffer:
+    """A receive buffer for the in-place feed path: ``nbytes`` of pinned host memory on the NUMA node of
+    ``near``'s GPU (nhip_host_alloc_near; ``near``: a Context, or a group member's handle from
+    ``Group.member``).  Wire bytes received into it are DMA'd as they lie by ``Batch.from_wire`` /
+    ``GroupStream.submit_wire``.  ``array`` is a writable uint8 numpy view, ``view`` a memoryview."""
+
+    def __init__(self, near, nbytes: int):
+        self.lib = _lib.load()
+        h = ctypes.c_void_p()
+        handle = near.handle if hasattr(near, "handle") else near
+        self.nbytes = int(nbytes)
+        check(self.lib.nhip_host_alloc_near(handle, max(self.nbytes, 1), ctypes.byref(h)), "nhip_host_alloc_near")
+        self.ptr = h.value
+        buf = (ctypes.c_uint8 * max(self.nbytes, 1)).from_address(self.ptr)
+        self.array = np.frombuffer(buf, dtype=np.uint8, count=self.nbytes)
+        self.view = memoryview(self.array)
+
+    def scan_txs(self, max_txs: int = None, span_cap: int = None, start: int = 0, end: int = None,
+                 raw: bool = False):
+        """wire_scan_txs over this buffer's bytes [start, end)."""
+        return wire_scan_txs(self.array[:self.nbytes if end is None else end], max_txs, span_cap, start, raw)
+
+    def scan_blocks(self, pow_tree_height: int, end: int = None):
+        """wire_scan_blocks over this buffer's bytes [0, end)."""
+        return wire_scan_blocks(self.array[:self.nbytes if end is None else end], pow_tree_height)
+
+    def close(self):
+        if self.ptr:
+            self.view, self.array = None, None
+            self.lib.nhip_host_free(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def le_words_gpu(ctx, data, spans) -> np.ndarray:
+    """nhip_le_words_gpu: the words of `spans` ((byte offset, words) pairs of `data`) gathered and reduced
+    mod p on the GPU, back to back in span order; bit-exact with nhip_le_words."""
+    addr, n, keep = _wire_source(data)
+    arr, k = _span_array(spans)
+    # a span that leaves the buffer is the library's NHIP_ERR_ARG: no output is sized from it
+    inside = all(arr[i].offset <= n and arr[i].len <= (n - arr[i].offset) // 8 for i in range(k))
+    total = sum(int(arr[i].len) for i in range(k)) if inside else 0
+    out = np.zeros(max(total, 1), dtype=np.uint64)
+    check(ctx.lib.nhip_le_words_gpu(ctx.handle, addr, n, arr, k, out.ctypes.data), "nhip_le_words_gpu")
+    return out[:total]
+
+
 class Batch:
     """Device-resident batch: decode + upload once, run the device phases any number of times."""
 
@@ -196,6 +319,42 @@ class Batch:
         check(self.ctx.lib.nhip_batch_refill(self.ctx.handle, self.handle, self.air.handle, ctypes.byref(params),
                                              m.claims, m.proofs, m.n), "nhip_batch_refill")
         self.n = m.n
+
+    @classmethod
+    def from_wire(cls, ctx, air: Air, stark: Stark, claims, data, spans) -> "Batch":
+        """A batch whose proof i is spans[i] = (byte offset, words) of the wire bytes `data` (a
+        WireBuffer: DMA'd as it lies; any other buffer: through the pinned staging), gathered into
+        aligned words on the device (nhip_batch_prepare_wire).  Canonical input form only."""
+        self = cls.__new__(cls)
+        self.ctx, self.air, self.stark = ctx, air, stark
+        m = _claims_only(claims)
+        addr, nb, keep = _wire_source(data)
+        arr, k = _span_array(spans)
+        if m.n < k:
+            raise ValueError("fewer claims than spans")
+        self.n = 0
+        self.handle = None
+        h = ctypes.c_void_p()
+        params = stark.c()
+        check(ctx.lib.nhip_batch_prepare_wire(ctx.handle, air.handle, ctypes.byref(params), m.claims, addr, nb, arr, k,
+                                              ctypes.byref(h)), "nhip_batch_prepare_wire")
+        self.handle = h.value
+        self.n = k
+        return self
+
+    def refill_wire(self, claims, data, spans) -> None:
+        """Replace the batch's proofs in place from wire bytes (nhip_batch_refill_wire; the batch must
+        be idle).  `data` may be reused when this returns."""
+        m = _claims_only(claims)
+        addr, nb, keep = _wire_source(data)
+        arr, k = _span_array(spans)
+        if m.n < k:
+            raise ValueError("fewer claims than spans")
+        params = self.stark.c()
+        self.n = 0
+        check(self.ctx.lib.nhip_batch_refill_wire(self.ctx.handle, self.handle, self.air.handle, ctypes.byref(params),
+                                                  m.claims, addr, nb, arr, k), "nhip_batch_refill_wire")
+        self.n = k
 
     def run(self) -> Tuple[np.ndarray, bool]:
         v = np.zeros(max(self.n, 1), dtype=np.uint8)
@@ -389,6 +548,13 @@ class Group:
     def __len__(self) -> int:
         return int(self.lib.nhip_group_size(self.handle))
 
+    def member(self, i: int) -> int:
+        """Member i's context handle (borrowed; e.g. the ``near`` of a WireBuffer)."""
+        h = self.lib.nhip_group_member(self.handle, i)
+        if not h:
+            raise IndexError("group member out of range")
+        return h
+
     def numa(self) -> List[dict]:
         """Per member: its GPU's NUMA node and CPUs (the member's threads and staging live there)."""
         from . import numa_of
@@ -471,6 +637,29 @@ class GroupStream:
         check(self.lib.nhip_group_stream_submit_placed(self.handle, claims.claims, placed.proofs,
                                                        ctypes.addressof(placed.member_of), n, v.ctypes.data,
                                                        ctypes.addressof(ok)), "nhip_group_stream_submit_placed")
+        prev, self._prev = self._prev, (v[:n], ok, n)
+        return None if prev is None else ([bool(x) for x in prev[0]], bool(prev[1][0]))
+
+    def submit_wire(self, claims, data, spans, member_of: Sequence[int] = None):
+        """nhip_group_stream_submit_wire: proof i = spans[i] of the wire bytes `data` (a WireBuffer or
+        any byte buffer), on member member_of[i] or, when None, by the LPT rule on the span lengths.
+        `data` may be overwritten as soon as this returns.  Returns the previous batch's result."""
+        m = _claims_only(claims)
+        addr, nb, keep = _wire_source(data)
+        arr, n = _span_array(spans)
+        if m.n < n:
+            raise ValueError("fewer claims than spans")
+        mo = None
+        if member_of is not None:
+            if len(member_of) != n:
+                raise ValueError("member_of must have one entry per span")
+            mo = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in member_of])
+        v = np.zeros(max(n, 1), dtype=np.uint8)
+        ok = (ctypes.c_uint8 * 1)()
+        check(self.lib.nhip_group_stream_submit_wire(self.handle, m.claims, addr, nb, arr,
+                                                     ctypes.addressof(mo) if mo is not None else None, n,
+                                                     v.ctypes.data, ctypes.addressof(ok)),
+              "nhip_group_stream_submit_wire")
         prev, self._prev = self._prev, (v[:n], ok, n)
         return None if prev is None else ([bool(x) for x in prev[0]], bool(prev[1][0]))
 

@@ -151,6 +151,14 @@ pub struct nhip_tx {
     pub seq_words: u64,
 }
 
+/// A run of field words inside a byte buffer: byte offset of the first word (any alignment), words.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug, PartialEq, Eq)]
+pub struct nhip_span {
+    pub offset: u64,
+    pub len: u64,
+}
+
 #[repr(C)]
 #[derive(Default, Clone, Copy, Debug)]
 pub struct nhip_pow_mast_paths {
@@ -274,6 +282,27 @@ extern "C" {
     pub fn nhip_blk_claims(bytes: *const u8, n_bytes: usize, block: *const nhip_blk_block, words: *mut u64,
                            claims: *mut nhip_claim) -> c_int;
     pub fn nhip_le_words(bytes: *const u8, n_bytes: usize, offset: u64, n: usize, out: *mut u64) -> c_int;
+    pub fn nhip_le_words_gpu(ctx: *mut nhip_ctx, bytes: *const u8, n_bytes: usize, spans: *const nhip_span, n: usize,
+                             out: *mut u64) -> c_int;
+    pub fn nhip_wire_scan_txs(bytes: *const u8, n_bytes: usize, max_txs: usize, spans: *mut nhip_span,
+                              span_cap: usize, n_txs: *mut usize, n_proofs: *mut usize, consumed: *mut usize) -> c_int;
+    pub fn nhip_wire_scan_blocks(bytes: *const u8, n_bytes: usize, pow_tree_height: u32, spans: *mut nhip_span,
+                                 block_of: *mut u64, span_cap: usize, n_proofs: *mut usize,
+                                 n_blocks: *mut usize) -> c_int;
+    pub fn nhip_verify_batch_wire(ctx: *mut nhip_ctx, air: *mut nhip_air, params: *const nhip_stark_params,
+                                  claims: *const nhip_claim, bytes: *const u8, n_bytes: usize,
+                                  spans: *const nhip_span, n: usize, verdicts: *mut u8,
+                                  stats: *mut nhip_stats) -> c_int;
+    pub fn nhip_batch_prepare_wire(ctx: *mut nhip_ctx, air: *mut nhip_air, params: *const nhip_stark_params,
+                                   claims: *const nhip_claim, bytes: *const u8, n_bytes: usize,
+                                   spans: *const nhip_span, n: usize, out: *mut *mut nhip_batch) -> c_int;
+    pub fn nhip_batch_refill_wire(ctx: *mut nhip_ctx, batch: *mut nhip_batch, air: *mut nhip_air,
+                                  params: *const nhip_stark_params, claims: *const nhip_claim, bytes: *const u8,
+                                  n_bytes: usize, spans: *const nhip_span, n: usize) -> c_int;
+    pub fn nhip_group_stream_submit_wire(stream: *mut nhip_group_stream, claims: *const nhip_claim,
+                                         bytes: *const u8, n_bytes: usize, spans: *const nhip_span,
+                                         member_of: *const u32, n: usize, verdicts: *mut u8,
+                                         all_ok: *mut u8) -> c_int;
     pub fn nhip_tx_scan(bytes: *const u8, n_bytes: usize, tx: *mut nhip_tx) -> c_int;
     pub fn nhip_arena_create(group: *mut nhip_group, bytes_per_member: usize, out: *mut *mut nhip_arena) -> c_int;
     pub fn nhip_arena_destroy(arena: *mut nhip_arena);

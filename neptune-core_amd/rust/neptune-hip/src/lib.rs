@@ -443,6 +443,101 @@ impl GpuNode {
         }
         Ok(())
     }
+
+    /// `verify_wire_batches` without the host decode copy: every batch of back-to-back
+    /// `TransferTransaction` bytes is received by `receive(k, buf)` straight into one of two pinned
+    /// buffers of `buffer_bytes` (`nhip_host_alloc_near` on member 0's socket; it returns the bytes
+    /// written, 0 = no more batches), scanned for its proof spans (`nhip_wire_scan_txs`, no word
+    /// copied) and submitted as it lies (`nhip_group_stream_submit_wire`): the device gathers the
+    /// unaligned words.  Two host-DRAM passes per proof byte (the receive, the DMA) instead of four.
+    /// Batch k + 1 is received and scanned while batch k uploads.  `claims` and `on_verdicts` as in
+    /// `verify_wire_batches`.
+    pub fn verify_wire_in_place<R, C, F>(&self, buffer_bytes: usize, mut receive: R, mut claims: C,
+                                         mut on_verdicts: F) -> Result<(), GpuFault>
+    where
+        R: FnMut(usize, &mut [u8]) -> usize + Send,
+        C: FnMut(usize, &[u8]) -> Vec<Claim>,
+        F: FnMut(usize, Vec<bool>, bool),
+    {
+        struct Pinned(*mut u8, usize);
+        unsafe impl Send for Pinned {}
+        unsafe impl Sync for Pinned {}
+        impl Drop for Pinned {
+            fn drop(&mut self) {
+                unsafe { sys::nhip_host_free(self.0 as *mut _) };
+            }
+        }
+        struct Stream(*mut sys::nhip_group_stream);
+        impl Drop for Stream {
+            fn drop(&mut self) {
+                unsafe { sys::nhip_group_stream_destroy(self.0) }
+            }
+        }
+        let near = unsafe { sys::nhip_group_member(self.group, 0) };
+        let new_buf = || -> Result<Pinned, GpuFault> {
+            let mut p = ptr::null_mut();
+            ok(unsafe { sys::nhip_host_alloc_near(near, buffer_bytes.max(1), &mut p) })?;
+            Ok(Pinned(p as *mut u8, buffer_bytes))
+        };
+        let bufs = [new_buf()?, new_buf()?];
+        let mut params = self.params;
+        params.input_form = sys::NHIP_INPUT_CANONICAL;
+        let mut st = ptr::null_mut();
+        ok(unsafe { sys::nhip_group_stream_create(self.group, self.air.0, &params, &mut st) })?;
+        let st = Stream(st);
+        // receive batch k into its buffer and find its proofs: (bytes, spans)
+        let mut fill = |k: usize, b: &Pinned| -> Result<(usize, Vec<sys::nhip_span>), GpuFault> {
+            let buf = unsafe { std::slice::from_raw_parts_mut(b.0, b.1) };
+            let len = receive(k, buf).min(b.1);
+            let cap = len / 8 + 1;
+            let mut spans = vec![sys::nhip_span::default(); cap];
+            let (mut ntx, mut np, mut used) = (0usize, 0usize, 0usize);
+            ok(unsafe {
+                sys::nhip_wire_scan_txs(b.0, len, usize::MAX, spans.as_mut_ptr(), cap, &mut ntx, &mut np, &mut used)
+            })?;
+            spans.truncate(np);
+            Ok((len, spans))
+        };
+        let mut results: [(Vec<u8>, u8); 2] = [(Vec::new(), 0), (Vec::new(), 0)];
+        let mut next = Some(fill(0, &bufs[0])?);
+        let mut k = 0usize;
+        while let Some((len, spans)) = next.take() {
+            if len == 0 {
+                break;
+            }
+            let slot = k & 1;
+            let bytes = unsafe { std::slice::from_raw_parts(bufs[slot].0, len) };
+            let cs: Vec<sys::nhip_claim> = canonical_claims(&claims(k, bytes));
+            if cs.len() != spans.len() {
+                return Err(GpuFault(sys::NHIP_ERR_ARG));
+            }
+            results[slot].0 = vec![0u8; spans.len()];
+            let (vp, ap) = (results[slot].0.as_mut_ptr(), &mut results[slot].1 as *mut u8);
+            // batch k uploads (and batch k - 1's verdicts come back) while batch k + 1 is received
+            let (submitted, filled) = std::thread::scope(|scope| {
+                let (fill, other) = (&mut fill, &bufs[slot ^ 1]);
+                let h = scope.spawn(move || fill(k + 1, other));
+                let rc = unsafe {
+                    sys::nhip_group_stream_submit_wire(st.0, cs.as_ptr(), bufs[slot].0, len, spans.as_ptr(),
+                                                       ptr::null(), spans.len(), vp, ap)
+                };
+                (ok(rc), h.join().unwrap_or(Err(GpuFault(sys::NHIP_ERR_HIP))))
+            });
+            submitted?;
+            next = Some(filled?);
+            if k > 0 {
+                let (v, all) = &results[slot ^ 1];
+                on_verdicts(k - 1, v.iter().map(|&b| b == 1).collect(), *all == 1);
+            }
+            k += 1;
+        }
+        ok(unsafe { sys::nhip_group_stream_finish(st.0) })?;
+        if let Some(last) = k.checked_sub(1) {
+            let (v, all) = &results[last & 1];
+            on_verdicts(last, v.iter().map(|&b| b == 1).collect(), *all == 1);
+        }
+        Ok(())
+    }
 }
 
 /// Claims as canonical words (for the wire-bytes path, whose proof words are canonical): the
