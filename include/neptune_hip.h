@@ -587,6 +587,74 @@ int nhip_absolute_index_sets(nhip_ctx *ctx, const uint64_t *items, const uint64_
                              const uint64_t *receiver_preimages, const uint64_t *aocl_leaf_indices, size_t n,
                              uint64_t *minimum_out, uint32_t *distances_out);
 
+/* ---- mutator-set checks (neptune-core/src/util_types/mutator_set/) ---------
+ * The step after "the proof verifies": can the inputs be removed from the mutator set.  Digests are
+ * canonical u64 x 5.  Variable-length data is CSR-shaped: an off[n + 1] array (off[0] = 0,
+ * non-decreasing) in units of digests (paths) or of u32 indices (chunks).  The device computes
+ * every verdict; the host checks shapes only (NHIP_ERR_ARG: a null pointer with a non-zero count,
+ * offsets that do not start at 0 or decrease) and a HIP error is NHIP_ERR_HIP, never a verdict.
+ *
+ * Fail closed where the reference would panic or truncate: `(index / CHUNK_SIZE) as u64`
+ * (mutator_set/shared.rs:24) truncates for indices >= 2^76, and ActiveWindow::contains
+ * (active_window.rs:153-159) asserts index < WINDOW_SIZE, which an index in chunk
+ * batch_index + 256 (accepted by split_by_activity, absolute_index_set.rs:140-160) violates.  Here a
+ * record with any index whose untruncated chunk index exceeds batch_index + 255, or whose
+ * minimum + distance saturates u128, is rejected with NHIP_MS_OUT_OF_RANGE. */
+typedef struct {
+    const uint64_t *peaks; /* n_peaks digests, tallest peak first */
+    uint32_t n_peaks;
+    uint64_t num_leafs;
+} nhip_mmr;
+/* MutatorSetAccumulator (mutator_set_accumulator.rs:32-36): the AOCL, the inactive part of the
+ * sliding-window Bloom filter, and the active window's index list (ActiveWindow::sbf, any order) */
+typedef struct {
+    nhip_mmr aocl, swbf_inactive;
+    const uint32_t *active;
+    uint64_t n_active;
+} nhip_msa;
+/* The chunk dictionaries (removal_record/chunk_dictionary.rs:27-33) of n records, flattened: record
+ * i owns the entries entry_off[i] .. entry_off[i + 1], in dictionary order. */
+typedef struct {
+    const uint64_t *entry_off;   /* n + 1 */
+    const uint64_t *chunk_index; /* per entry */
+    const uint64_t *path_off;    /* entries + 1, in digests */
+    const uint64_t *path;        /* MMR authentication paths, leaf sibling first */
+    const uint64_t *rel_off;     /* entries + 1, in u32 */
+    const uint32_t *rel;         /* Chunk::relative_indices */
+} nhip_ms_chunks;
+/* status byte of a record; of several failures the first in this order is reported:
+ * NOT_IN_AOCL, OUT_OF_RANGE, ABSENT_CHUNK, BAD_MMR_PATH, ALREADY_REMOVED */
+enum {
+    NHIP_MS_OK = 0,
+    NHIP_MS_ABSENT_CHUNK = 1,    /* RemovalRecordValidityError::AbsentAuthenticatedChunk */
+    NHIP_MS_BAD_MMR_PATH = 2,    /* RemovalRecordValidityError::InvalidSwbfiMmrMp */
+    NHIP_MS_ALREADY_REMOVED = 3, /* every index is set: no absent index */
+    NHIP_MS_OUT_OF_RANGE = 4,    /* a future index (AbsoluteRemovalIndexIsFutureIndex), or see above */
+    NHIP_MS_NOT_IN_AOCL = 5      /* verify only: leaf index or AOCL membership */
+};
+/* twenty-first MmrMembershipProof::verify(leaf_index, leaf, peaks, num_leafs) for n (leaf, path)
+ * items against one MMR, as called bare in application/loops/peer_loop.rs:1235 and
+ * protocol/peer.rs:824.  Path shape: util_types/archival_mmr.rs:250-281.  path_off: n + 1. */
+int nhip_mmr_verify_batch(nhip_ctx *ctx, const nhip_mmr *mmr, const uint64_t *leaf_index, const uint64_t *leaves,
+                          const uint64_t *path_off, const uint64_t *path, size_t n, uint8_t *verdicts);
+/* RemovalRecord::validate (removal_record.rs:202-251) and MutatorSetAccumulator::can_remove
+ * (mutator_set_accumulator.rs:187-222) for n removal records, as in Block::validate
+ * (protocol/consensus/block/mod.rs:816-822) and the mempool's per-tip check
+ * (protocol/consensus/transaction/transaction_kernel.rs:129,145).  minimum: n x 2 u64 (u128,
+ * little-endian) and distances: n x 45 u32, the AbsoluteIndexSet layout the index-set entry point
+ * above writes.  valid / can_remove / status: n bytes each. */
+int nhip_ms_can_remove_batch(nhip_ctx *ctx, const nhip_msa *msa, const uint64_t *minimum, const uint32_t *distances,
+                             const nhip_ms_chunks *chunks, size_t n, uint8_t *valid, uint8_t *can_remove,
+                             uint8_t *status);
+/* MutatorSetAccumulator::verify (mutator_set_accumulator.rs:252-339) for n (item, membership
+ * proof) pairs, as the wallet runs it for every monitored UTXO on every block
+ * (state/wallet/wallet_state.rs:1796,1958; state/mod.rs:1050,1206,1341).  The index sets are
+ * derived on the device (AbsoluteIndexSet::compute).  aocl_path_off: n + 1, in digests. */
+int nhip_ms_verify_batch(nhip_ctx *ctx, const nhip_msa *msa, const uint64_t *items, const uint64_t *sender_randomness,
+                         const uint64_t *receiver_preimages, const uint64_t *aocl_leaf_index,
+                         const uint64_t *aocl_path_off, const uint64_t *aocl_path, const nhip_ms_chunks *chunks,
+                         size_t n, uint8_t *verdicts, uint8_t *status);
+
 /* ---- kernel timing (HIP events on the ctx stream around every kernel launch) ------------ */
 int nhip_timing_enable(nhip_ctx *ctx, int on);
 /* Total device time of the kernels launched since the last reset, and their count. */

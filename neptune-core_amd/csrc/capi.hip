@@ -16,6 +16,7 @@
 #include "device_scope.hpp"
 #include "host_numa.hpp"
 #include "kernels.hpp"
+#include "ms_shape.hpp"
 #include "wire.hpp"
 
 struct nhip_ctx {
@@ -150,7 +151,9 @@ extern "C" {
 // nhip_batch_set_graph
 // 2400: the in-place feed path (nhip_span, nhip_le_words_gpu, nhip_wire_scan_*, nhip_verify_batch_wire,
 // nhip_batch_prepare_wire, nhip_batch_refill_wire, nhip_group_stream_submit_wire)
-int nhip_abi_version(void) { return 2400; }
+// 2500: the mutator-set checks (nhip_mmr, nhip_msa, nhip_ms_chunks, NHIP_MS_*, nhip_mmr_verify_batch,
+// nhip_ms_can_remove_batch, nhip_ms_verify_batch)
+int nhip_abi_version(void) { return 2500; }
 
 int nhip_set_fs_form(int form) { return nhip::set_fs_form(form) == 0 ? NHIP_OK : NHIP_ERR_ARG; }
 int nhip_set_climb_from_ops(int64_t ops) { return nhip::set_climb_from_ops(ops) == 0 ? NHIP_OK : NHIP_ERR_ARG; }
@@ -656,6 +659,227 @@ int nhip_absolute_index_sets(nhip_ctx* c, const uint64_t* items, const uint64_t*
     if (e == hipSuccess) e = hipMemcpyAsync(distances_out, p[3], sizes[3], hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     return hip_fail(e);
+}
+
+// ------------------------------------------------------------------ mutator-set checks
+namespace {
+
+// Host-to-device copies of one call; the first HIP error sticks and later copies are skipped.
+struct Uploader {
+    hipStream_t st;
+    hipError_t e = hipSuccess;
+    void operator()(void* dst, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+    }
+};
+
+// Ends a staged call: the stream is drained on every path (the sources may be this call's own
+// temporaries), and a HIP error is never a verdict.
+int ms_finish(nhip_ctx* c, int rc, hipError_t e) {
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    return hip_fail(e != hipSuccess ? e : es);
+}
+
+}  // namespace
+
+// twenty-first MmrMembershipProof::verify for n (leaf, path) items against one MMR
+// (application/loops/peer_loop.rs:1235, protocol/peer.rs:824; path shape archival_mmr.rs:250-281).
+int nhip_mmr_verify_batch(nhip_ctx* c, const nhip_mmr* mmr, const uint64_t* leaf_index, const uint64_t* leaves,
+                          const uint64_t* path_off, const uint64_t* path, size_t n, uint8_t* verdicts) {
+    if (!c || nhip::ms_mmr_ok(mmr)) return NHIP_ERR_ARG;
+    if (n == 0) return NHIP_OK;
+    if (!leaf_index || !leaves || !verdicts || n > SIZE_MAX / 64) return NHIP_ERR_ARG;
+    uint64_t pd = 0;
+    if (nhip::ms_paths_ok(path_off, path, n, &pd)) return NHIP_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    const DeviceScope device_scope(c->device);
+    size_t sizes[6] = {(size_t)mmr->n_peaks * 40, n * 8, n * 40, (n + 1) * 8, (size_t)pd * 40, n};
+    void* p[6];
+    int rc = carve(c, sizes, p);
+    if (rc) return rc;
+    Uploader up{c->stream};
+    up(p[0], mmr->peaks, sizes[0]);
+    up(p[1], leaf_index, sizes[1]);
+    up(p[2], leaves, sizes[2]);
+    up(p[3], path_off, sizes[3]);
+    up(p[4], path, sizes[4]);
+    if (up.e != hipSuccess) return ms_finish(c, NHIP_OK, up.e);
+    const nhip::MmrDev dm{(const uint64_t*)p[0], mmr->n_peaks, mmr->num_leafs};
+    rc = timed_launch(c, [&] {
+        return nhip::launch_mmr_verify(dm, (const uint64_t*)p[1], (const uint64_t*)p[2], (const uint64_t*)p[3],
+                                       (const uint64_t*)p[4], n, (uint8_t*)p[5], c->stream);
+    });
+    hipError_t e = hipSuccess;
+    if (rc == NHIP_OK) e = hipMemcpyAsync(verdicts, p[5], n, hipMemcpyDeviceToHost, c->stream);
+    return ms_finish(c, rc, e);
+}
+
+// RemovalRecord::validate (removal_record.rs:202-251) and MutatorSetAccumulator::can_remove
+// (mutator_set_accumulator.rs:187-222) for n records (block/mod.rs:816-822, transaction_kernel.rs:129,145):
+// k_ms_chunk_auth over every dictionary entry, then k_ms_records.
+int nhip_ms_can_remove_batch(nhip_ctx* c, const nhip_msa* msa, const uint64_t* minimum, const uint32_t* distances,
+                             const nhip_ms_chunks* chunks, size_t n, uint8_t* valid, uint8_t* can_remove,
+                             uint8_t* status) {
+    if (!c || nhip::ms_msa_ok(msa)) return NHIP_ERR_ARG;
+    if (n == 0) return NHIP_OK;
+    if (!minimum || !distances || !valid || !can_remove || !status || n > SIZE_MAX / 256) return NHIP_ERR_ARG;
+    nhip::MsChunkCounts cc;
+    if (nhip::ms_chunks_ok(chunks, n, &cc)) return NHIP_ERR_ARG;
+    try {
+        // membership is order-free: the kernel searches a sorted copy of the active window
+        std::vector<uint32_t> active(msa->active, msa->active + (msa->n_active ? msa->n_active : 0));
+        std::sort(active.begin(), active.end());
+        const size_t E = (size_t)cc.entries;
+        std::lock_guard<std::mutex> g(c->mu);
+        const DeviceScope device_scope(c->device);
+        size_t sizes[12] = {(size_t)msa->swbf_inactive.n_peaks * 40, active.size() * 4, n * 16, n * 45 * 4,
+                            (n + 1) * 8, E * 8, (E + 1) * 8, (size_t)cc.path_digests * 40, (E + 1) * 8,
+                            (size_t)cc.rel_words * 4, E, 3 * n};
+        void* p[12];
+        int rc = carve(c, sizes, p);
+        if (rc) return rc;
+        Uploader up{c->stream};
+        up(p[0], msa->swbf_inactive.peaks, sizes[0]);
+        up(p[1], active.data(), sizes[1]);
+        up(p[2], minimum, sizes[2]);
+        up(p[3], distances, sizes[3]);
+        up(p[4], chunks->entry_off, sizes[4]);
+        up(p[5], chunks->chunk_index, sizes[5]);
+        up(p[6], chunks->path_off, sizes[6]);
+        up(p[7], chunks->path, sizes[7]);
+        up(p[8], chunks->rel_off, sizes[8]);
+        up(p[9], chunks->rel, sizes[9]);
+        if (up.e != hipSuccess) return ms_finish(c, NHIP_OK, up.e);
+        const nhip::MmrDev swbf{(const uint64_t*)p[0], msa->swbf_inactive.n_peaks, msa->swbf_inactive.num_leafs};
+        rc = timed_launch(c, [&] {
+            return nhip::launch_ms_chunk_auth(swbf, (const uint64_t*)p[5], (const uint64_t*)p[6], (const uint64_t*)p[7],
+                                              (const uint64_t*)p[8], (const uint32_t*)p[9], E, (uint8_t*)p[10],
+                                              c->stream);
+        });
+        uint8_t* out = (uint8_t*)p[11];
+        if (rc == NHIP_OK) {
+            nhip::MsRecordsDev r{};
+            r.minimum = (const uint64_t*)p[2];
+            r.distances = (const uint32_t*)p[3];
+            r.entry_off = (const uint64_t*)p[4];
+            r.chunk_index = (const uint64_t*)p[5];
+            r.rel_off = (const uint64_t*)p[8];
+            r.rel = (const uint32_t*)p[9];
+            r.auth = (const uint8_t*)p[10];
+            r.aocl_member = nullptr;
+            r.active = (const uint32_t*)p[1];
+            r.n_active = active.size();
+            r.aocl_num_leafs = msa->aocl.num_leafs;
+            r.valid = out;
+            r.verdict = out + n;
+            r.status = out + 2 * n;
+            rc = timed_launch(c, [&] { return nhip::launch_ms_records(r, n, c->stream); });
+        }
+        hipError_t e = hipSuccess;
+        if (rc == NHIP_OK) e = hipMemcpyAsync(valid, out, n, hipMemcpyDeviceToHost, c->stream);
+        if (rc == NHIP_OK && e == hipSuccess) e = hipMemcpyAsync(can_remove, out + n, n, hipMemcpyDeviceToHost, c->stream);
+        if (rc == NHIP_OK && e == hipSuccess) e = hipMemcpyAsync(status, out + 2 * n, n, hipMemcpyDeviceToHost, c->stream);
+        return ms_finish(c, rc, e);
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// MutatorSetAccumulator::verify (mutator_set_accumulator.rs:252-339) for n (item, membership proof) pairs
+// (wallet_state.rs:1796,1958; state/mod.rs:1050,1206,1341): k_ms_aocl_leaf, AbsoluteIndexSet::compute into
+// device buffers (no host round trip), k_ms_chunk_auth, k_ms_records.
+int nhip_ms_verify_batch(nhip_ctx* c, const nhip_msa* msa, const uint64_t* items, const uint64_t* sender_randomness,
+                         const uint64_t* receiver_preimages, const uint64_t* aocl_leaf_index,
+                         const uint64_t* aocl_path_off, const uint64_t* aocl_path, const nhip_ms_chunks* chunks,
+                         size_t n, uint8_t* verdicts, uint8_t* status) {
+    if (!c || nhip::ms_msa_ok(msa)) return NHIP_ERR_ARG;
+    if (n == 0) return NHIP_OK;
+    if (!items || !sender_randomness || !receiver_preimages || !aocl_leaf_index || !verdicts || !status ||
+        n > SIZE_MAX / 256)
+        return NHIP_ERR_ARG;
+    uint64_t apd = 0;
+    if (nhip::ms_paths_ok(aocl_path_off, aocl_path, n, &apd)) return NHIP_ERR_ARG;
+    nhip::MsChunkCounts cc;
+    if (nhip::ms_chunks_ok(chunks, n, &cc)) return NHIP_ERR_ARG;
+    try {
+        std::vector<uint32_t> active(msa->active, msa->active + (msa->n_active ? msa->n_active : 0));
+        std::sort(active.begin(), active.end());
+        std::vector<uint64_t> in(15 * n);
+        for (size_t i = 0; i < n; ++i)
+            for (int q = 0; q < 5; ++q) {
+                in[15 * i + q] = items[5 * i + q];
+                in[15 * i + 5 + q] = sender_randomness[5 * i + q];
+                in[15 * i + 10 + q] = receiver_preimages[5 * i + q];
+            }
+        const size_t E = (size_t)cc.entries;
+        std::lock_guard<std::mutex> g(c->mu);
+        const DeviceScope device_scope(c->device);
+        size_t sizes[18] = {(size_t)msa->aocl.n_peaks * 40, (size_t)msa->swbf_inactive.n_peaks * 40, active.size() * 4,
+                            15 * n * 8, n * 8, (n + 1) * 8, (size_t)apd * 40, (n + 1) * 8, E * 8, (E + 1) * 8,
+                            (size_t)cc.path_digests * 40, (E + 1) * 8, (size_t)cc.rel_words * 4,
+                            n * 16, n * 45 * 4, n, E, 2 * n};
+        void* p[18];
+        int rc = carve(c, sizes, p);
+        if (rc) return rc;
+        Uploader up{c->stream};
+        up(p[0], msa->aocl.peaks, sizes[0]);
+        up(p[1], msa->swbf_inactive.peaks, sizes[1]);
+        up(p[2], active.data(), sizes[2]);
+        up(p[3], in.data(), sizes[3]);
+        up(p[4], aocl_leaf_index, sizes[4]);
+        up(p[5], aocl_path_off, sizes[5]);
+        up(p[6], aocl_path, sizes[6]);
+        up(p[7], chunks->entry_off, sizes[7]);
+        up(p[8], chunks->chunk_index, sizes[8]);
+        up(p[9], chunks->path_off, sizes[9]);
+        up(p[10], chunks->path, sizes[10]);
+        up(p[11], chunks->rel_off, sizes[11]);
+        up(p[12], chunks->rel, sizes[12]);
+        if (up.e != hipSuccess) return ms_finish(c, NHIP_OK, up.e);
+        const nhip::MmrDev aocl{(const uint64_t*)p[0], msa->aocl.n_peaks, msa->aocl.num_leafs};
+        const nhip::MmrDev swbf{(const uint64_t*)p[1], msa->swbf_inactive.n_peaks, msa->swbf_inactive.num_leafs};
+        rc = timed_launch(c, [&] {
+            return nhip::launch_ms_aocl_leaf(aocl, (const uint64_t*)p[3], (const uint64_t*)p[4], (const uint64_t*)p[5],
+                                             (const uint64_t*)p[6], n, (uint8_t*)p[15], c->stream);
+        });
+        if (rc == NHIP_OK)
+            rc = timed_launch(c, [&] {
+                return nhip::launch_absolute_index_sets((const uint64_t*)p[3], (const uint64_t*)p[4], n,
+                                                        (uint64_t*)p[13], (uint32_t*)p[14], c->stream);
+            });
+        if (rc == NHIP_OK)
+            rc = timed_launch(c, [&] {
+                return nhip::launch_ms_chunk_auth(swbf, (const uint64_t*)p[8], (const uint64_t*)p[9],
+                                                  (const uint64_t*)p[10], (const uint64_t*)p[11],
+                                                  (const uint32_t*)p[12], E, (uint8_t*)p[16], c->stream);
+            });
+        uint8_t* out = (uint8_t*)p[17];
+        if (rc == NHIP_OK) {
+            nhip::MsRecordsDev r{};
+            r.minimum = (const uint64_t*)p[13];
+            r.distances = (const uint32_t*)p[14];
+            r.entry_off = (const uint64_t*)p[7];
+            r.chunk_index = (const uint64_t*)p[8];
+            r.rel_off = (const uint64_t*)p[11];
+            r.rel = (const uint32_t*)p[12];
+            r.auth = (const uint8_t*)p[16];
+            r.aocl_member = (const uint8_t*)p[15];
+            r.active = (const uint32_t*)p[2];
+            r.n_active = active.size();
+            r.aocl_num_leafs = msa->aocl.num_leafs;
+            r.valid = nullptr;
+            r.verdict = out;
+            r.status = out + n;
+            rc = timed_launch(c, [&] { return nhip::launch_ms_records(r, n, c->stream); });
+        }
+        hipError_t e = hipSuccess;
+        if (rc == NHIP_OK) e = hipMemcpyAsync(verdicts, out, n, hipMemcpyDeviceToHost, c->stream);
+        if (rc == NHIP_OK && e == hipSuccess) e = hipMemcpyAsync(status, out + n, n, hipMemcpyDeviceToHost, c->stream);
+        return ms_finish(c, rc, e);
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
 }
 
 }  // extern "C"

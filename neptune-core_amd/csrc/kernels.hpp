@@ -27,6 +27,39 @@ hipError_t launch_mast_roots(const uint64_t* d_leaves, uint32_t fields, uint32_t
 hipError_t launch_absolute_index_sets(const uint64_t* d_digests, const uint64_t* d_aocl, size_t n, uint64_t* d_min,
                                       uint32_t* d_dist, hipStream_t st);
 
+// ---- mutator-set checks (ms_kernels.hip); every pointer a device pointer
+struct MmrDev {
+    const uint64_t* peaks;  // n_peaks canonical digests, tallest peak first
+    uint32_t n_peaks;
+    uint64_t num_leafs;
+};
+struct MsRecordsDev {
+    const uint64_t* minimum;    // n x 2 (u128, little-endian)
+    const uint32_t* distances;  // n x 45
+    const uint64_t* entry_off;  // n + 1
+    const uint64_t* chunk_index;
+    const uint64_t* rel_off;
+    const uint32_t* rel;
+    const uint8_t* auth;         // per entry, from k_ms_chunk_auth
+    const uint8_t* aocl_member;  // per record, from k_ms_aocl_leaf: verify; nullptr: validate / can_remove
+    const uint32_t* active;      // the active window's indices, sorted ascending
+    uint64_t n_active;
+    uint64_t aocl_num_leafs;
+    uint8_t* valid;  // validate (nullptr with aocl_member)
+    uint8_t* verdict;
+    uint8_t* status;
+};
+hipError_t launch_mmr_verify(const MmrDev& mmr, const uint64_t* d_leaf_index, const uint64_t* d_leaves,
+                             const uint64_t* d_path_off, const uint64_t* d_path, size_t n, uint8_t* d_verdicts,
+                             hipStream_t st);
+hipError_t launch_ms_aocl_leaf(const MmrDev& aocl, const uint64_t* d_digests, const uint64_t* d_leaf_index,
+                               const uint64_t* d_path_off, const uint64_t* d_path, size_t n, uint8_t* d_member,
+                               hipStream_t st);
+hipError_t launch_ms_chunk_auth(const MmrDev& swbf, const uint64_t* d_chunk_index, const uint64_t* d_path_off,
+                                const uint64_t* d_path, const uint64_t* d_rel_off, const uint32_t* d_rel,
+                                size_t entries, uint8_t* d_auth, hipStream_t st);
+hipError_t launch_ms_records(const MsRecordsDev& r, size_t n, hipStream_t st);
+
 // ---- batched STARK verifier (stark_kernels.hip)
 static constexpr uint32_t AIR_LDS_HEADER = (16 + 4 + 4 + 4) * 24 + 16;  // red (per wave), zinv, derived, misc, flag
 static constexpr uint32_t AIR_LDS_BUDGET = 160 * 1024 - 8192;              // k_ood_air dynamic LDS cap

@@ -1,0 +1,33 @@
+// Shape checks of the mutator-set entry points (nhip_mmr_verify_batch, nhip_ms_can_remove_batch,
+// nhip_ms_verify_batch): the only thing the host decides about their inputs.  Every verdict is the
+// device's; the host refuses (NHIP_ERR_ARG) what it could not stage without reading outside the
+// caller's arrays: a null pointer with a non-zero count, an offset array that does not start at 0
+// or decreases, and totals whose byte size leaves size_t.  Host only (no HIP), so that
+// tests/native/ms_shape_check.cpp links it under ASan + UBSan.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/neptune_hip.h"
+
+namespace nhip {
+
+// off[0..n]: off[0] == 0, non-decreasing, and off[n] * unit_bytes fits size_t.  *total = off[n].
+int ms_csr_ok(const uint64_t* off, size_t n, size_t unit_bytes, uint64_t* total);
+
+// peaks present when n_peaks != 0
+int ms_mmr_ok(const nhip_mmr* mmr);
+// both MMRs, and the active window's list present when n_active != 0
+int ms_msa_ok(const nhip_msa* msa);
+
+// n (leaf, path) items: path_off covers n paths, path present when it holds any digest
+int ms_paths_ok(const uint64_t* path_off, const uint64_t* path, size_t n, uint64_t* path_digests);
+
+struct MsChunkCounts {
+    uint64_t entries = 0, path_digests = 0, rel_words = 0;
+};
+// the flattened chunk dictionaries of n records: entry_off covers the records, path_off and rel_off
+// cover the entry_off[n] entries, and every array that has an element is present
+int ms_chunks_ok(const nhip_ms_chunks* chunks, size_t n, MsChunkCounts* counts);
+
+}  // namespace nhip

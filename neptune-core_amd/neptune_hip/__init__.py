@@ -308,3 +308,10 @@ class MTree:
     @staticmethod
     def verify_batch(root, indices, paths, elements, depth: int) -> np.ndarray:
         return default_context().mtree_verify(root, indices, elements, paths, depth)
+
+
+# the mutator-set checks (MMR membership, can_remove, verify) live in neptune_hip.mutator_set
+from . import mutator_set  # noqa: E402
+from .mutator_set import MmrAccumulator, MutatorSetAccumulator  # noqa: E402,F401
+
+__all__ += ["mutator_set", "MmrAccumulator", "MutatorSetAccumulator"]

@@ -95,6 +95,22 @@ class Span(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
 
+class Mmr(ctypes.Structure):
+    """nhip_mmr: an MMR accumulator (peaks tallest first)."""
+    _fields_ = [("peaks", ctypes.c_void_p), ("n_peaks", ctypes.c_uint32), ("num_leafs", ctypes.c_uint64)]
+
+
+class Msa(ctypes.Structure):
+    """nhip_msa: MutatorSetAccumulator."""
+    _fields_ = [("aocl", Mmr), ("swbf_inactive", Mmr), ("active", ctypes.c_void_p), ("n_active", ctypes.c_uint64)]
+
+
+class MsChunks(ctypes.Structure):
+    """nhip_ms_chunks: the chunk dictionaries of n records, flattened (CSR)."""
+    _fields_ = [("entry_off", ctypes.c_void_p), ("chunk_index", ctypes.c_void_p), ("path_off", ctypes.c_void_p),
+                ("path", ctypes.c_void_p), ("rel_off", ctypes.c_void_p), ("rel", ctypes.c_void_p)]
+
+
 _pp = ctypes.POINTER(ctypes.c_void_p)
 
 # (name, argtypes) for every symbol of include/neptune_hip.h
@@ -166,6 +182,11 @@ SIGNATURES = {
                              ctypes.c_int),
     "nhip_absolute_index_sets": ([_vp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz,
                                   ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "nhip_mmr_verify_batch": ([_vp, ctypes.POINTER(Mmr), _vp, _vp, _vp, _vp, _sz, _vp], ctypes.c_int),
+    "nhip_ms_can_remove_batch": ([_vp, ctypes.POINTER(Msa), _vp, _vp, ctypes.POINTER(MsChunks), _sz, _vp, _vp, _vp],
+                                 ctypes.c_int),
+    "nhip_ms_verify_batch": ([_vp, ctypes.POINTER(Msa), _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MsChunks), _sz,
+                              _vp, _vp], ctypes.c_int),
     "nhip_proof_decodes": ([_vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof)],
                            ctypes.c_int),
     "nhip_verify_batch": ([_vp, _vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof),

@@ -141,6 +141,17 @@ def validate_block_file(ctx, path: str, verifier, programs, network=None,
                                  network if network is not None else Network.MAIN)
 
 
+def inputs_removable(ctx, msa_before, removal_records) -> Tuple[bool, Optional[int]]:
+    """`Block::validate` rule 2.b (protocol/consensus/block/mod.rs:816-822): every input of the block
+    passes `msa_before.can_remove`, all records in one GPU call.  Returns `(True, None)`, or `False` and
+    the position of the first record that fails (the one the reference's loop stops at)."""
+    from .mutator_set import can_remove_batch
+    for i, (_, can, _) in enumerate(can_remove_batch(ctx, msa_before, removal_records)):
+        if not can:
+            return False, i
+    return True, None
+
+
 @dataclass
 class TransferTransaction:
     """transfer_transaction.rs:31-47: `kernel_sequences` (the kernel's 8 MAST sequences) and the

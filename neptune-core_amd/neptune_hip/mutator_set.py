@@ -1,0 +1,207 @@
+"""Host mirror of neptune-core's mutator-set checks (util_types/mutator_set/) over the C ABI: the
+consensus step after "the proof verifies", batched.
+
+* `mmr_verify_batch(ctx, mmr, items)` — twenty-first `MmrMembershipProof::verify`, as called bare in
+  application/loops/peer_loop.rs:1235 and protocol/peer.rs:824.
+* `can_remove_batch(ctx, msa, records)` — `RemovalRecord::validate` (removal_record.rs:202-251) and
+  `MutatorSetAccumulator::can_remove` (mutator_set_accumulator.rs:187-222) for many records:
+  protocol/consensus/block/mod.rs:816-822, transaction_kernel.rs:129,145.
+* `verify_batch(ctx, msa, items, proofs)` — `MutatorSetAccumulator::verify`
+  (mutator_set_accumulator.rs:252-339): state/wallet/wallet_state.rs:1796,1958.
+
+The types mirror the reference's over numpy; every verdict is the device's.  Where the reference
+would panic or truncate (an index past the active window, or >= 2^76) the record is rejected with
+`OUT_OF_RANGE`.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass, field
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from .mast import NUM_TRIALS, AbsoluteIndexSet
+
+CHUNK_SIZE = 1 << 12
+BATCH_SIZE = 1 << 3
+OK, ABSENT_CHUNK, BAD_MMR_PATH, ALREADY_REMOVED, OUT_OF_RANGE, NOT_IN_AOCL = range(6)
+STATUS_NAMES = ("OK", "ABSENT_CHUNK", "BAD_MMR_PATH", "ALREADY_REMOVED", "OUT_OF_RANGE", "NOT_IN_AOCL")
+
+
+def _digests(x, n=None) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(x, dtype=np.uint64)).reshape(-1, 5)
+    if n is not None and a.shape[0] != n:
+        raise ValueError("digest count")
+    return a
+
+
+@dataclass
+class MmrAccumulator:
+    """twenty-first `MmrAccumulator`: the peaks (tallest first) and the leaf count."""
+    peaks: Sequence[Sequence[int]]
+    num_leafs: int
+
+    def _c(self):
+        p = _digests(self.peaks) if len(self.peaks) else np.zeros((0, 5), dtype=np.uint64)
+        return _lib.Mmr(p.ctypes.data if p.size else None, p.shape[0], int(self.num_leafs)), p
+
+
+@dataclass
+class MutatorSetAccumulator:
+    """mutator_set_accumulator.rs:32-36; `swbf_active` is `ActiveWindow::sbf`."""
+    aocl: MmrAccumulator
+    swbf_inactive: MmrAccumulator
+    swbf_active: Sequence[int] = ()
+
+    @property
+    def batch_index(self) -> int:
+        """`get_batch_index` (util_types/mutator_set.rs:74-76)."""
+        return max(int(self.aocl.num_leafs) - 1, 0) // BATCH_SIZE
+
+    def _c(self):
+        a, ka = self.aocl._c()
+        s, ks = self.swbf_inactive._c()
+        act = np.ascontiguousarray(np.asarray(self.swbf_active, dtype=np.uint32)).reshape(-1)
+        return _lib.Msa(a, s, act.ctypes.data if act.size else None, act.size), (ka, ks, act)
+
+
+@dataclass
+class Chunk:
+    relative_indices: Sequence[int] = ()
+
+
+@dataclass
+class RemovalRecord:
+    """removal_record.rs:40-43.  `target_chunks`: the chunk dictionary in its order, entries
+    `(chunk_index, mmr_path, Chunk)` with `mmr_path` a list of digests (leaf sibling first)."""
+    absolute_indices: AbsoluteIndexSet
+    target_chunks: List[Tuple[int, Sequence[Sequence[int]], Chunk]] = field(default_factory=list)
+
+
+@dataclass
+class MsMembershipProof:
+    """ms_membership_proof.rs:51-57: randomness, the AOCL authentication path and the chunk dictionary."""
+    sender_randomness: Sequence[int]
+    receiver_preimage: Sequence[int]
+    auth_path_aocl: Sequence[Sequence[int]]
+    aocl_leaf_index: int
+    target_chunks: List[Tuple[int, Sequence[Sequence[int]], Chunk]] = field(default_factory=list)
+
+
+@dataclass
+class PackedChunks:
+    """The chunk dictionaries of n records, flattened (`nhip_ms_chunks`)."""
+    entry_off: np.ndarray
+    chunk_index: np.ndarray
+    path_off: np.ndarray
+    path: np.ndarray
+    rel_off: np.ndarray
+    rel: np.ndarray
+
+    def _c(self):
+        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        return _lib.MsChunks(ptr(self.entry_off), ptr(self.chunk_index), ptr(self.path_off), ptr(self.path),
+                             ptr(self.rel_off), ptr(self.rel))
+
+
+def pack_paths(paths: Sequence[Sequence[Sequence[int]]]) -> Tuple[np.ndarray, np.ndarray]:
+    """CSR form of ragged digest paths: `off[n + 1]` in digests, the digests back to back."""
+    off = np.zeros(len(paths) + 1, dtype=np.uint64)
+    if len(paths):
+        off[1:] = np.cumsum([len(p) for p in paths], dtype=np.uint64)
+    flat = [d for p in paths for d in p]
+    data = _digests(flat) if flat else np.zeros((0, 5), dtype=np.uint64)
+    return off, data
+
+
+def pack_chunks(records) -> PackedChunks:
+    """Pure CSR packing of the `target_chunks` of `records` (RemovalRecords or MsMembershipProofs)."""
+    entries = [e for r in records for e in r.target_chunks]
+    entry_off = np.zeros(len(records) + 1, dtype=np.uint64)
+    if len(records):
+        entry_off[1:] = np.cumsum([len(r.target_chunks) for r in records], dtype=np.uint64)
+    chunk_index = np.asarray([int(ci) for ci, _, _ in entries], dtype=np.uint64)
+    path_off, path = pack_paths([p for _, p, _ in entries])
+    rel_off = np.zeros(len(entries) + 1, dtype=np.uint64)
+    if entries:
+        rel_off[1:] = np.cumsum([len(c.relative_indices) for _, _, c in entries], dtype=np.uint64)
+    rel = np.asarray([int(x) for _, _, c in entries for x in c.relative_indices], dtype=np.uint32)
+    return PackedChunks(entry_off, chunk_index, path_off, path, rel_off, rel)
+
+
+def unpack_chunks(packed: PackedChunks) -> List[List[Tuple[int, List[Tuple[int, ...]], Chunk]]]:
+    """Inverse of `pack_chunks`: the `target_chunks` list of every record."""
+    out = []
+    for i in range(len(packed.entry_off) - 1):
+        tc = []
+        for e in range(int(packed.entry_off[i]), int(packed.entry_off[i + 1])):
+            p = packed.path[int(packed.path_off[e]):int(packed.path_off[e + 1])]
+            r = packed.rel[int(packed.rel_off[e]):int(packed.rel_off[e + 1])]
+            tc.append((int(packed.chunk_index[e]), [tuple(int(x) for x in d) for d in p], Chunk([int(x) for x in r])))
+        out.append(tc)
+    return out
+
+
+def _ptr(a: np.ndarray):
+    return a.ctypes.data if a.size else None
+
+
+def mmr_verify_batch(ctx, mmr: MmrAccumulator, items) -> List[bool]:
+    """`items`: `(leaf_index, leaf_digest, path)` triples, all against `mmr`."""
+    n = len(items)
+    if n == 0:
+        return []
+    cm, _keep = mmr._c()
+    leaf_index = np.asarray([int(i) for i, _, _ in items], dtype=np.uint64)
+    leaves = _digests([l for _, l, _ in items], n)
+    off, path = pack_paths([p for _, _, p in items])
+    v = np.zeros(n, dtype=np.uint8)
+    check(ctx.lib.nhip_mmr_verify_batch(ctx.handle, ctypes.byref(cm), leaf_index.ctypes.data, leaves.ctypes.data,
+                                        off.ctypes.data, _ptr(path), n, v.ctypes.data), "nhip_mmr_verify_batch")
+    return [bool(x) for x in v]
+
+
+def can_remove_batch(ctx, msa: MutatorSetAccumulator, records: Sequence[RemovalRecord]) -> List[Tuple[bool, bool, int]]:
+    """`(validate, can_remove, status)` of every record against `msa`."""
+    n = len(records)
+    if n == 0:
+        return []
+    cm, _keep = msa._c()
+    mn = np.zeros((n, 2), dtype=np.uint64)
+    dist = np.zeros((n, NUM_TRIALS), dtype=np.uint32)
+    for i, r in enumerate(records):
+        m = int(r.absolute_indices.minimum)
+        mn[i] = (m & (2 ** 64 - 1), m >> 64)
+        dist[i] = np.asarray(r.absolute_indices.distances, dtype=np.uint32)
+    packed = pack_chunks(records)
+    cc = packed._c()
+    valid, can, status = (np.zeros(n, dtype=np.uint8) for _ in range(3))
+    check(ctx.lib.nhip_ms_can_remove_batch(ctx.handle, ctypes.byref(cm), mn.ctypes.data, dist.ctypes.data,
+                                           ctypes.byref(cc), n, valid.ctypes.data, can.ctypes.data,
+                                           status.ctypes.data), "nhip_ms_can_remove_batch")
+    return [(bool(valid[i]), bool(can[i]), int(status[i])) for i in range(n)]
+
+
+def verify_batch(ctx, msa: MutatorSetAccumulator, items, proofs: Sequence[MsMembershipProof]) -> List[Tuple[bool, int]]:
+    """`(verdict, status)` of `msa.verify(item, proof)` for every pair."""
+    n = len(proofs)
+    if len(items) != n:
+        raise ValueError("one membership proof per item")
+    if n == 0:
+        return []
+    cm, _keep = msa._c()
+    it = _digests(items, n)
+    sr = _digests([p.sender_randomness for p in proofs], n)
+    rp = _digests([p.receiver_preimage for p in proofs], n)
+    leaf = np.asarray([int(p.aocl_leaf_index) for p in proofs], dtype=np.uint64)
+    off, path = pack_paths([p.auth_path_aocl for p in proofs])
+    packed = pack_chunks(proofs)
+    cc = packed._c()
+    v, status = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    check(ctx.lib.nhip_ms_verify_batch(ctx.handle, ctypes.byref(cm), it.ctypes.data, sr.ctypes.data, rp.ctypes.data,
+                                       leaf.ctypes.data, off.ctypes.data, _ptr(path), ctypes.byref(cc), n,
+                                       v.ctypes.data, status.ctypes.data), "nhip_ms_verify_batch")
+    return [(bool(v[i]), int(status[i])) for i in range(n)]

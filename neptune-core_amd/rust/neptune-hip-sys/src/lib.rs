@@ -167,6 +167,44 @@ pub struct nhip_pow_mast_paths {
     pub kernel: [[u64; 5]; 1],
 }
 
+/// An MMR accumulator: `n_peaks` digests (tallest peak first) and the leaf count.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_mmr {
+    pub peaks: *const u64,
+    pub n_peaks: u32,
+    pub num_leafs: u64,
+}
+
+/// `MutatorSetAccumulator`: the AOCL, the inactive SWBF, and the active window's index list.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_msa {
+    pub aocl: nhip_mmr,
+    pub swbf_inactive: nhip_mmr,
+    pub active: *const u32,
+    pub n_active: u64,
+}
+
+/// The chunk dictionaries of n records, flattened (CSR offsets in entries, digests and u32 indices).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_ms_chunks {
+    pub entry_off: *const u64,
+    pub chunk_index: *const u64,
+    pub path_off: *const u64,
+    pub path: *const u64,
+    pub rel_off: *const u64,
+    pub rel: *const u32,
+}
+
+pub const NHIP_MS_OK: u8 = 0;
+pub const NHIP_MS_ABSENT_CHUNK: u8 = 1;
+pub const NHIP_MS_BAD_MMR_PATH: u8 = 2;
+pub const NHIP_MS_ALREADY_REMOVED: u8 = 3;
+pub const NHIP_MS_OUT_OF_RANGE: u8 = 4;
+pub const NHIP_MS_NOT_IN_AOCL: u8 = 5;
+
 extern "C" {
     pub fn nhip_init(device_mask: u32, out: *mut *mut nhip_ctx) -> c_int;
     pub fn nhip_destroy(ctx: *mut nhip_ctx);
@@ -342,6 +380,17 @@ extern "C" {
     pub fn nhip_absolute_index_sets(ctx: *mut nhip_ctx, items: *const u64, sender_randomness: *const u64,
                                     receiver_preimages: *const u64, aocl_leaf_indices: *const u64, n: usize,
                                     minimum_out: *mut u64, distances_out: *mut u32) -> c_int;
+    pub fn nhip_mmr_verify_batch(ctx: *mut nhip_ctx, mmr: *const nhip_mmr, leaf_index: *const u64,
+                                 leaves: *const u64, path_off: *const u64, path: *const u64, n: usize,
+                                 verdicts: *mut u8) -> c_int;
+    pub fn nhip_ms_can_remove_batch(ctx: *mut nhip_ctx, msa: *const nhip_msa, minimum: *const u64,
+                                    distances: *const u32, chunks: *const nhip_ms_chunks, n: usize,
+                                    valid: *mut u8, can_remove: *mut u8, status: *mut u8) -> c_int;
+    pub fn nhip_ms_verify_batch(ctx: *mut nhip_ctx, msa: *const nhip_msa, items: *const u64,
+                                sender_randomness: *const u64, receiver_preimages: *const u64,
+                                aocl_leaf_index: *const u64, aocl_path_off: *const u64, aocl_path: *const u64,
+                                chunks: *const nhip_ms_chunks, n: usize, verdicts: *mut u8,
+                                status: *mut u8) -> c_int;
     pub fn nhip_timing_enable(ctx: *mut nhip_ctx, on: c_int) -> c_int;
     pub fn nhip_timing_read(ctx: *mut nhip_ctx, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
 }
