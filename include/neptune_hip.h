@@ -630,7 +630,13 @@ enum {
     NHIP_MS_BAD_MMR_PATH = 2,    /* RemovalRecordValidityError::InvalidSwbfiMmrMp */
     NHIP_MS_ALREADY_REMOVED = 3, /* every index is set: no absent index */
     NHIP_MS_OUT_OF_RANGE = 4,    /* a future index (AbsoluteRemovalIndexIsFutureIndex), or see above */
-    NHIP_MS_NOT_IN_AOCL = 5      /* verify only: leaf index or AOCL membership */
+    NHIP_MS_NOT_IN_AOCL = 5,     /* verify only: leaf index or AOCL membership */
+    /* nhip_ms_apply_batch only (a job's status) */
+    NHIP_MS_INCONSISTENT = 6,      /* msa_before: popcount(num_leafs) != n_peaks, swbf_inactive.num_leafs != batch
+                                      index, or num_leafs + additions wraps */
+    NHIP_MS_DUPLICATE_RECORD = 7,  /* Block::validate 2.c: two records with equal index arrays */
+    NHIP_MS_UPDATE_IMPOSSIBLE = 8, /* 2.d: a record whose indices are all set once the earlier ones are applied */
+    NHIP_MS_UPDATE_MISMATCH = 9    /* 2.e: the accumulator after is not the expected one */
 };
 /* twenty-first MmrMembershipProof::verify(leaf_index, leaf, peaks, num_leafs) for n (leaf, path)
  * items against one MMR, as called bare in application/loops/peer_loop.rs:1235 and
@@ -654,6 +660,60 @@ int nhip_ms_verify_batch(nhip_ctx *ctx, const nhip_msa *msa, const uint64_t *ite
                          const uint64_t *receiver_preimages, const uint64_t *aocl_leaf_index,
                          const uint64_t *aocl_path_off, const uint64_t *aocl_path, const nhip_ms_chunks *chunks,
                          size_t n, uint8_t *verdicts, uint8_t *status);
+
+/* ---- batched mutator-set updates --------------------------------------------
+ * Block::validate rules 2.b-2.e (protocol/consensus/block/mod.rs:816-849) and
+ * Block::mutator_set_accumulator_after (mod.rs:369-378) for n_jobs independent jobs: job j is
+ * (msa_before[j], the addition records add_off[j] .. add_off[j + 1], the removal records
+ * rec_off[j] .. rec_off[j + 1] in block order, optionally msa_expected[j]).  The end state is computed
+ * directly (MutatorSetUpdate::apply_to_accumulator, block/mutator_set_update.rs:107-153, without its
+ * record-by-record proof maintenance).  Per job, in this order, the first failure is the status:
+ *   1. NHIP_MS_INCONSISTENT (see the enum);
+ *   2. 2.b: every record as nhip_ms_can_remove_batch decides it against msa_before[j]: the first failing
+ *      record's status, bad_record = its index in the job;
+ *   3. 2.c: NHIP_MS_DUPLICATE_RECORD, bad_record = the first record equal to an earlier one;
+ *   4. 2.d: NHIP_MS_UPDATE_IMPOSSIBLE, bad_record = the first record all of whose indices are set in
+ *      msa_before[j] or occur in an earlier record of the job;
+ *   5. the accumulator after; with msa_expected, 2.e: NHIP_MS_UPDATE_MISMATCH unless both num_leafs, both
+ *      peak lists, the window's length and its words in the given order are equal.
+ * Divergences from the reference, both failing closed: (a) an inconsistent msa_before is a status, where
+ * the reference asserts (removal_record.rs:66-70); (b) the window after is sorted ascending
+ * (ActiveWindow::insert, active_window.rs:115-124), so an unsorted expected window never matches, although
+ * the reference would carry an unsorted window through a block that inserts nothing (no operation of the
+ * reference produces one).  Inactive chunks are taken as sorted, as Chunk::insert (chunk.rs:55-64) leaves them.
+ * The accumulators after are written for jobs whose status is NHIP_MS_OK or NHIP_MS_UPDATE_MISMATCH; for the
+ * others the counts are 0.  With no expected accumulator and no removal records the call is
+ * Block::mutator_set_accumulator_after.  Shape errors (NHIP_ERR_ARG, outputs untouched): a null pointer with
+ * a non-zero count, offsets that do not start at 0 or decrease, a window capacity below
+ * n_active + 45 records of its job. */
+typedef struct {
+    size_t n_jobs;
+    const nhip_msa *msa_before;   /* n_jobs */
+    const uint64_t *add_off;      /* n_jobs + 1, in addition records */
+    const uint64_t *additions;    /* AdditionRecord::canonical_commitment, 5 words each */
+    const uint64_t *rec_off;      /* n_jobs + 1, in removal records */
+    const uint64_t *minimum;      /* records x 2 u64 (u128, little-endian) */
+    const uint32_t *distances;    /* records x 45 */
+    const nhip_ms_chunks *chunks; /* the dictionaries of all records */
+    const nhip_msa *msa_expected; /* n_jobs, or NULL */
+} nhip_ms_apply_in;
+typedef struct {
+    uint8_t *verdict;             /* n_jobs: 1 = every step passed */
+    uint8_t *status;              /* n_jobs: NHIP_MS_* */
+    uint64_t *bad_record;         /* n_jobs: index in the job, UINT64_MAX = none */
+    /* the accumulators after: all NULL, or all present */
+    uint64_t *aocl_peaks;         /* n_jobs x 64 digests */
+    uint32_t *aocl_n_peaks;       /* n_jobs */
+    uint64_t *aocl_num_leafs;     /* n_jobs */
+    uint64_t *swbf_peaks;         /* n_jobs x 64 digests */
+    uint32_t *swbf_n_peaks;       /* n_jobs */
+    uint64_t *swbf_num_leafs;     /* n_jobs */
+    const uint64_t *active_off;   /* n_jobs + 1: job j's window goes to active[active_off[j] ..], capacity
+                                     active_off[j + 1] - active_off[j] >= n_active + 45 records */
+    uint32_t *active;
+    uint64_t *n_active;           /* n_jobs */
+} nhip_ms_apply_out;
+int nhip_ms_apply_batch(nhip_ctx *ctx, const nhip_ms_apply_in *in, nhip_ms_apply_out *out);
 
 /* ---- kernel timing (HIP events on the ctx stream around every kernel launch) ------------ */
 int nhip_timing_enable(nhip_ctx *ctx, int on);

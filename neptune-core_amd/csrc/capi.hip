@@ -153,7 +153,8 @@ extern "C" {
 // nhip_batch_prepare_wire, nhip_batch_refill_wire, nhip_group_stream_submit_wire)
 // 2500: the mutator-set checks (nhip_mmr, nhip_msa, nhip_ms_chunks, NHIP_MS_*, nhip_mmr_verify_batch,
 // nhip_ms_can_remove_batch, nhip_ms_verify_batch)
-int nhip_abi_version(void) { return 2500; }
+// 2600: batched mutator-set updates (nhip_ms_apply_in, nhip_ms_apply_out, nhip_ms_apply_batch, four NHIP_MS_*)
+int nhip_abi_version(void) { return 2600; }
 
 int nhip_set_fs_form(int form) { return nhip::set_fs_form(form) == 0 ? NHIP_OK : NHIP_ERR_ARG; }
 int nhip_set_climb_from_ops(int64_t ops) { return nhip::set_climb_from_ops(ops) == 0 ? NHIP_OK : NHIP_ERR_ARG; }
@@ -877,6 +878,199 @@ int nhip_ms_verify_batch(nhip_ctx* c, const nhip_msa* msa, const uint64_t* items
         if (rc == NHIP_OK) e = hipMemcpyAsync(verdicts, out, n, hipMemcpyDeviceToHost, c->stream);
         if (rc == NHIP_OK && e == hipSuccess) e = hipMemcpyAsync(status, out + n, n, hipMemcpyDeviceToHost, c->stream);
         return ms_finish(c, rc, e);
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// Block::validate rules 2.b-2.e and Block::mutator_set_accumulator_after for independent jobs (DESIGN.md
+// §6d): k_ms_chunk_auth_jobs, k_ms_records_jobs, k_ms_apply.  The host stages order only: sorted copies of
+// the active windows, each job's index slots sorted by (index, record) and grouped by chunk index, and its
+// records sorted by their index arrays.  It hashes nothing and decides nothing.
+int nhip_ms_apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out) {
+    using u128 = unsigned __int128;
+    nhip::MsApplyCounts cnt;
+    if (!c || nhip::ms_apply_ok(in, out, &cnt)) return NHIP_ERR_ARG;
+    const size_t n = in->n_jobs;
+    if (n == 0) return NHIP_OK;
+    try {
+        const size_t R = (size_t)cnt.records, E = (size_t)cnt.chunks.entries;
+        std::vector<nhip::MsApplyJob> jobs(n);
+        std::vector<uint64_t> peaks;
+        std::vector<uint32_t> active, exp_active, rec_job(R), entry_rec(E), idx_perm(45 * R), grp, rec_perm(R);
+        std::vector<u128> vals;
+        uint64_t dig_total = 0, grp_total = 0, win_total = 0;
+        auto put_peaks = [&](const nhip_mmr& m) {
+            const uint64_t off = peaks.size() / 5;
+            if (m.n_peaks) peaks.insert(peaks.end(), m.peaks, m.peaks + 5 * (size_t)m.n_peaks);
+            return off;
+        };
+        for (size_t j = 0; j < n; ++j) {
+            const nhip_msa& b = in->msa_before[j];
+            nhip::MsApplyJob& jb = jobs[j];
+            jb = nhip::MsApplyJob{};
+            jb.aocl_n = b.aocl.num_leafs;
+            jb.swbf_n = b.swbf_inactive.num_leafs;
+            jb.aocl_np = b.aocl.n_peaks;
+            jb.swbf_np = b.swbf_inactive.n_peaks;
+            jb.aocl_peaks = put_peaks(b.aocl);
+            jb.swbf_peaks = put_peaks(b.swbf_inactive);
+            jb.act_off = active.size();
+            jb.n_active = b.n_active;
+            if (b.n_active) active.insert(active.end(), b.active, b.active + b.n_active);
+            std::sort(active.begin() + jb.act_off, active.end());
+            jb.add_off = in->add_off[j];
+            jb.k = in->add_off[j + 1] - in->add_off[j];
+            jb.rec_off = in->rec_off[j];
+            jb.m = in->rec_off[j + 1] - in->rec_off[j];
+            if (in->msa_expected) {
+                const nhip_msa& x = in->msa_expected[j];
+                jb.exp_aocl_n = x.aocl.num_leafs;
+                jb.exp_swbf_n = x.swbf_inactive.num_leafs;
+                jb.exp_aocl_np = x.aocl.n_peaks;
+                jb.exp_swbf_np = x.swbf_inactive.n_peaks;
+                jb.exp_aocl_peaks = put_peaks(x.aocl);
+                jb.exp_swbf_peaks = put_peaks(x.swbf_inactive);
+                jb.exp_act_off = exp_active.size();
+                jb.exp_n_active = x.n_active;
+                if (x.n_active) exp_active.insert(exp_active.end(), x.active, x.active + x.n_active);
+            }
+            // order only: the job's index slots by (index, record), the runs of one chunk index, the records
+            // by their index arrays
+            const size_t m = (size_t)jb.m, r0 = (size_t)jb.rec_off;
+            vals.resize(45 * m);
+            for (size_t r = 0; r < m; ++r) {
+                rec_job[r0 + r] = (uint32_t)j;
+                const u128 mn = ((u128)in->minimum[2 * (r0 + r) + 1] << 64) | in->minimum[2 * (r0 + r)];
+                for (size_t t = 0; t < 45; ++t) vals[45 * r + t] = mn + in->distances[45 * (r0 + r) + t];
+                for (uint64_t e = in->chunks->entry_off[r0 + r]; e < in->chunks->entry_off[r0 + r + 1]; ++e)
+                    entry_rec[e] = (uint32_t)(r0 + r);
+            }
+            uint32_t* perm = idx_perm.data() + 45 * r0;
+            for (size_t s = 0; s < 45 * m; ++s) perm[s] = (uint32_t)s;
+            std::sort(perm, perm + 45 * m, [&](uint32_t x, uint32_t y) { return vals[x] != vals[y] ? vals[x] < vals[y] : x < y; });
+            jb.grp_off = grp_total;
+            for (size_t s = 0; s < 45 * m; ++s)
+                if (s == 0 || (vals[perm[s]] >> 12) != (vals[perm[s - 1]] >> 12)) {
+                    grp.push_back((uint32_t)s);
+                    ++jb.n_grp;
+                }
+            grp.push_back((uint32_t)(45 * m));
+            grp_total += jb.n_grp;
+            uint32_t* rp = rec_perm.data() + r0;
+            for (size_t r = 0; r < m; ++r) rp[r] = (uint32_t)r;
+            std::stable_sort(rp, rp + m, [&](uint32_t x, uint32_t y) {
+                return std::lexicographical_compare(vals.begin() + 45 * x, vals.begin() + 45 * x + 45,
+                                                    vals.begin() + 45 * y, vals.begin() + 45 * y + 45);
+            });
+            const uint64_t n1 = jb.aocl_n + jb.k;
+            const uint64_t slides =
+                n1 < jb.aocl_n ? 0 : (n1 ? n1 - 1 : 0) / 8 - (jb.aocl_n ? jb.aocl_n - 1 : 0) / 8;  // <= k / 8 + 1
+            jb.dig_off = dig_total;
+            dig_total += (jb.k + 1) + (2 * slides + 1) + 2 * jb.n_grp;
+            jb.win_off = cnt.accumulators ? out->active_off[j] : win_total;
+            jb.win_cap = cnt.accumulators ? out->active_off[j + 1] - out->active_off[j] : jb.n_active + 45 * jb.m;
+            win_total += jb.win_cap;
+        }
+        if (cnt.accumulators) win_total = cnt.window_cap;
+        const nhip_ms_chunks* ch = in->chunks;
+        std::lock_guard<std::mutex> g(c->mu);
+        const DeviceScope device_scope(c->device);
+        size_t sizes[29] = {n * sizeof(nhip::MsApplyJob), peaks.size() * 8, active.size() * 4, (size_t)cnt.additions * 40,
+                            R * 16, R * 45 * 4, R ? (R + 1) * 8 : 0, E * 8, R ? (E + 1) * 8 : 0,
+                            (size_t)cnt.chunks.path_digests * 40, R ? (E + 1) * 8 : 0, (size_t)cnt.chunks.rel_words * 4,
+                            R * 4, E * 4, R * 45 * 4, grp.size() * 4, R * 4, exp_active.size() * 4, E, 3 * R, 45 * R,
+                            (size_t)dig_total * 40, (size_t)grp_total * 16, 2 * n, n * 8, 2 * n * 64 * 40, 2 * n * 4,
+                            3 * n * 8, (size_t)win_total * 4};
+        void* p[29];
+        int rc = carve(c, sizes, p);
+        if (rc) return rc;
+        Uploader up{c->stream};
+        up(p[0], jobs.data(), sizes[0]);
+        up(p[1], peaks.data(), sizes[1]);
+        up(p[2], active.data(), sizes[2]);
+        up(p[3], in->additions, sizes[3]);
+        up(p[4], in->minimum, sizes[4]);
+        up(p[5], in->distances, sizes[5]);
+        if (R) {
+            up(p[6], ch->entry_off, sizes[6]);
+            up(p[7], ch->chunk_index, sizes[7]);
+            up(p[8], ch->path_off, sizes[8]);
+            up(p[9], ch->path, sizes[9]);
+            up(p[10], ch->rel_off, sizes[10]);
+            up(p[11], ch->rel, sizes[11]);
+        }
+        up(p[12], rec_job.data(), sizes[12]);
+        up(p[13], entry_rec.data(), sizes[13]);
+        up(p[14], idx_perm.data(), sizes[14]);
+        up(p[15], grp.data(), sizes[15]);
+        up(p[16], rec_perm.data(), sizes[16]);
+        up(p[17], exp_active.data(), sizes[17]);
+        if (up.e != hipSuccess) return ms_finish(c, NHIP_OK, up.e);
+        nhip::MsApplyDev a{};
+        a.jobs = (const nhip::MsApplyJob*)p[0];
+        a.peaks = (const uint64_t*)p[1];
+        a.active = (const uint32_t*)p[2];
+        a.additions = (const uint64_t*)p[3];
+        a.rec.minimum = (const uint64_t*)p[4];
+        a.rec.distances = (const uint32_t*)p[5];
+        a.rec.entry_off = (const uint64_t*)p[6];
+        a.rec.chunk_index = (const uint64_t*)p[7];
+        a.path_off = (const uint64_t*)p[8];
+        a.path = (const uint64_t*)p[9];
+        a.rec.rel_off = (const uint64_t*)p[10];
+        a.rec.rel = (const uint32_t*)p[11];
+        a.rec_job = (const uint32_t*)p[12];
+        a.entry_rec = (const uint32_t*)p[13];
+        a.idx_perm = (const uint32_t*)p[14];
+        a.grp = (const uint32_t*)p[15];
+        a.rec_perm = (const uint32_t*)p[16];
+        a.exp_active = (const uint32_t*)p[17];
+        a.has_expected = in->msa_expected ? 1 : 0;
+        a.rec.auth = (const uint8_t*)p[18];
+        a.rec.aocl_member = nullptr;
+        a.rec.valid = (uint8_t*)p[19];
+        a.rec.verdict = (uint8_t*)p[19] + R;
+        a.rec.status = (uint8_t*)p[19] + 2 * R;
+        a.index_set = (uint8_t*)p[20];
+        a.dig = (uint64_t*)p[21];
+        a.aux = (uint64_t*)p[22];
+        a.verdict = (uint8_t*)p[23];
+        a.status = (uint8_t*)p[23] + n;
+        a.bad = (uint64_t*)p[24];
+        a.out_peaks = (uint64_t*)p[25];
+        a.out_np = (uint32_t*)p[26];
+        a.out_n = (uint64_t*)p[27];
+        a.out_active = (uint32_t*)p[28];
+        rc = timed_launch(c, [&] { return nhip::launch_ms_chunk_auth_jobs(a, E, c->stream); });
+        if (rc == NHIP_OK) rc = timed_launch(c, [&] { return nhip::launch_ms_records_jobs(a, R, c->stream); });
+        if (rc == NHIP_OK) rc = timed_launch(c, [&] { return nhip::launch_ms_apply(a, n, c->stream); });
+        hipError_t e = hipSuccess;
+        auto down = [&](void* dst, const void* src, size_t bytes) {
+            if (rc == NHIP_OK && e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
+        };
+        // into temporaries first: the outputs stay untouched unless the whole call succeeds
+        std::vector<uint8_t> vs(2 * n);
+        std::vector<uint64_t> bad(n);
+        down(vs.data(), p[23], 2 * n);
+        down(bad.data(), p[24], n * 8);
+        if (cnt.accumulators) {
+            down(out->aocl_peaks, a.out_peaks, n * 64 * 40);
+            down(out->swbf_peaks, a.out_peaks + n * 64 * 5, n * 64 * 40);
+            down(out->aocl_n_peaks, a.out_np, n * 4);
+            down(out->swbf_n_peaks, a.out_np + n, n * 4);
+            down(out->aocl_num_leafs, a.out_n, n * 8);
+            down(out->swbf_num_leafs, a.out_n + n, n * 8);
+            down(out->n_active, a.out_n + 2 * n, n * 8);
+            down(out->active, a.out_active, (size_t)win_total * 4);
+        }
+        rc = ms_finish(c, rc, e);
+        if (rc == NHIP_OK) {
+            std::copy(vs.begin(), vs.begin() + n, out->verdict);
+            std::copy(vs.begin() + n, vs.end(), out->status);
+            std::copy(bad.begin(), bad.end(), out->bad_record);
+        }
+        return rc;
     } catch (const std::bad_alloc&) {
         return NHIP_ERR_OOM;
     }

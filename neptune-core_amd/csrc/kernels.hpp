@@ -60,6 +60,50 @@ hipError_t launch_ms_chunk_auth(const MmrDev& swbf, const uint64_t* d_chunk_inde
                                 size_t entries, uint8_t* d_auth, hipStream_t st);
 hipError_t launch_ms_records(const MsRecordsDev& r, size_t n, hipStream_t st);
 
+// ---- batched mutator-set updates (ms_apply_kernels.hip); every pointer a device pointer
+// One job as the host stages it: offsets into the pools of MsApplyDev (peaks and scratch in digests).
+struct MsApplyJob {
+    uint64_t aocl_n, swbf_n;          // msa_before: num_leafs
+    uint64_t aocl_peaks, swbf_peaks;  // ... and its peak lists in the peaks pool
+    uint64_t act_off, n_active;       // the sorted copy of its active window
+    uint64_t add_off, k;              // addition records
+    uint64_t rec_off, m;              // removal records (idx_perm: 45 rec_off; rec_perm: rec_off)
+    uint64_t grp_off, n_grp;          // groups before this job; its n_grp + 1 starts are grp[grp_off + job ..]
+    uint64_t dig_off;                 // digest scratch: k + 1, 2 slides + 1, 2 n_grp
+    uint64_t win_off, win_cap;        // the window after in out_active
+    uint64_t exp_aocl_n, exp_swbf_n, exp_aocl_peaks, exp_swbf_peaks, exp_act_off, exp_n_active;
+    uint32_t aocl_np, swbf_np, exp_aocl_np, exp_swbf_np;
+};
+struct MsApplyDev {
+    const MsApplyJob* jobs;
+    const uint64_t* peaks;       // canonical digests: every job's four peak lists
+    const uint32_t* active;      // every job's active window, sorted ascending
+    const uint64_t* additions;   // canonical commitments
+    MsRecordsDev rec;            // the records of all jobs, and k_ms_records_jobs' outputs
+    const uint64_t* path_off;
+    const uint64_t* path;
+    const uint32_t* rec_job;     // per record
+    const uint32_t* entry_rec;   // per dictionary entry
+    uint8_t* index_set;          // 45 per record (ms_record_decide)
+    const uint32_t* idx_perm;    // per job: its 45 m index slots (record-in-job x 45 + t) sorted by (index, record)
+    const uint32_t* grp;         // per job: the starts of the runs of one chunk index in that order, then 45 m
+    const uint32_t* rec_perm;    // per job: its records sorted by their index arrays (stable)
+    const uint32_t* exp_active;  // the expected windows in the caller's order
+    uint32_t has_expected;
+    uint64_t* dig;               // digest scratch
+    uint64_t* aux;               // 2 per group: dictionary entry, chunk index
+    uint8_t* verdict;
+    uint8_t* status;
+    uint64_t* bad;               // first bad record in the job, ~0 = none
+    uint64_t* out_peaks;         // 2 x n_jobs x 64 digests: AOCL, SWBF
+    uint32_t* out_np;            // 2 x n_jobs
+    uint64_t* out_n;             // 3 x n_jobs: aocl.num_leafs, swbf_inactive.num_leafs, n_active
+    uint32_t* out_active;
+};
+hipError_t launch_ms_chunk_auth_jobs(const MsApplyDev& a, size_t entries, hipStream_t st);
+hipError_t launch_ms_records_jobs(const MsApplyDev& a, size_t n_records, hipStream_t st);
+hipError_t launch_ms_apply(const MsApplyDev& a, size_t n_jobs, hipStream_t st);
+
 // ---- batched STARK verifier (stark_kernels.hip)
 static constexpr uint32_t AIR_LDS_HEADER = (16 + 4 + 4 + 4) * 24 + 16;  // red (per wave), zinv, derived, misc, flag
 static constexpr uint32_t AIR_LDS_BUDGET = 160 * 1024 - 8192;              // k_ood_air dynamic LDS cap

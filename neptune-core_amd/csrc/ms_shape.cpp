@@ -45,4 +45,44 @@ int ms_chunks_ok(const nhip_ms_chunks* chunks, size_t n, MsChunkCounts* counts) 
     return NHIP_OK;
 }
 
+int ms_apply_ok(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, MsApplyCounts* counts) {
+    if (!in || !out) return NHIP_ERR_ARG;
+    MsApplyCounts c;
+    const size_t n = in->n_jobs;
+    if (n == 0) {
+        if (counts) *counts = c;
+        return NHIP_OK;
+    }
+    if (n > (size_t)UINT32_MAX || !in->msa_before || !out->verdict || !out->status || !out->bad_record)
+        return NHIP_ERR_ARG;
+    if (ms_csr_ok(in->add_off, n, 5 * sizeof(uint64_t), &c.additions)) return NHIP_ERR_ARG;
+    if (c.additions && !in->additions) return NHIP_ERR_ARG;
+    if (ms_csr_ok(in->rec_off, n, 45 * sizeof(uint32_t), &c.records)) return NHIP_ERR_ARG;
+    if (c.records) {
+        if (!in->minimum || !in->distances) return NHIP_ERR_ARG;
+        if (ms_chunks_ok(in->chunks, (size_t)c.records, &c.chunks)) return NHIP_ERR_ARG;
+    }
+    const int given = (out->aocl_peaks != nullptr) + (out->aocl_n_peaks != nullptr) + (out->aocl_num_leafs != nullptr) +
+                      (out->swbf_peaks != nullptr) + (out->swbf_n_peaks != nullptr) + (out->swbf_num_leafs != nullptr) +
+                      (out->active_off != nullptr) + (out->n_active != nullptr);
+    if (given != 0 && given != 8) return NHIP_ERR_ARG;
+    c.accumulators = given == 8;
+    if (c.accumulators) {
+        if (ms_csr_ok(out->active_off, n, sizeof(uint32_t), &c.window_cap)) return NHIP_ERR_ARG;
+        if (c.window_cap && !out->active) return NHIP_ERR_ARG;
+    } else if (out->active) {
+        return NHIP_ERR_ARG;
+    }
+    for (size_t j = 0; j < n; ++j) {
+        if (ms_msa_ok(&in->msa_before[j])) return NHIP_ERR_ARG;
+        if (in->msa_expected && ms_msa_ok(&in->msa_expected[j])) return NHIP_ERR_ARG;
+        const uint64_t m = in->rec_off[j + 1] - in->rec_off[j];
+        if (m > (uint64_t)UINT32_MAX / 45) return NHIP_ERR_ARG;
+        const uint64_t need = in->msa_before[j].n_active + 45 * m;  // n_active <= SIZE_MAX / 8: no wrap
+        if (c.accumulators && out->active_off[j + 1] - out->active_off[j] < need) return NHIP_ERR_ARG;
+    }
+    if (counts) *counts = c;
+    return NHIP_OK;
+}
+
 }  // namespace nhip

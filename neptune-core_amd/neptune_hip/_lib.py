@@ -111,6 +111,22 @@ class MsChunks(ctypes.Structure):
                 ("path", ctypes.c_void_p), ("rel_off", ctypes.c_void_p), ("rel", ctypes.c_void_p)]
 
 
+class MsApplyIn(ctypes.Structure):
+    """nhip_ms_apply_in: the jobs of one nhip_ms_apply_batch call."""
+    _fields_ = [("n_jobs", ctypes.c_size_t), ("msa_before", ctypes.POINTER(Msa)), ("add_off", ctypes.c_void_p),
+                ("additions", ctypes.c_void_p), ("rec_off", ctypes.c_void_p), ("minimum", ctypes.c_void_p),
+                ("distances", ctypes.c_void_p), ("chunks", ctypes.POINTER(MsChunks)),
+                ("msa_expected", ctypes.POINTER(Msa))]
+
+
+class MsApplyOut(ctypes.Structure):
+    """nhip_ms_apply_out: per-job verdicts and, optionally, the accumulators after."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("status", ctypes.c_void_p), ("bad_record", ctypes.c_void_p),
+                ("aocl_peaks", ctypes.c_void_p), ("aocl_n_peaks", ctypes.c_void_p), ("aocl_num_leafs", ctypes.c_void_p),
+                ("swbf_peaks", ctypes.c_void_p), ("swbf_n_peaks", ctypes.c_void_p), ("swbf_num_leafs", ctypes.c_void_p),
+                ("active_off", ctypes.c_void_p), ("active", ctypes.c_void_p), ("n_active", ctypes.c_void_p)]
+
+
 _pp = ctypes.POINTER(ctypes.c_void_p)
 
 # (name, argtypes) for every symbol of include/neptune_hip.h
@@ -187,6 +203,7 @@ SIGNATURES = {
                                  ctypes.c_int),
     "nhip_ms_verify_batch": ([_vp, ctypes.POINTER(Msa), _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MsChunks), _sz,
                               _vp, _vp], ctypes.c_int),
+    "nhip_ms_apply_batch": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut)], ctypes.c_int),
     "nhip_proof_decodes": ([_vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof)],
                            ctypes.c_int),
     "nhip_verify_batch": ([_vp, _vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof),

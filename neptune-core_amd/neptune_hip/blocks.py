@@ -152,6 +152,27 @@ def inputs_removable(ctx, msa_before, removal_records) -> Tuple[bool, Optional[i
     return True, None
 
 
+def mutator_set_update_valid(ctx, msa_before, removal_records, addition_records, msa_claimed) -> Tuple[bool, int]:
+    """`Block::validate` rules 2.b-2.e (protocol/consensus/block/mod.rs:816-849) in the reference's order,
+    one GPU call: every input removable, the removal records distinct, the update applicable, and the
+    accumulator after it equal to `msa_claimed` (the one the block commits to).  Returns `(ok, status)`
+    with `status` one of `neptune_hip.mutator_set`'s."""
+    from .mutator_set import MutatorSetUpdate, apply_update_batch
+    update = MutatorSetUpdate(list(removal_records), list(addition_records))
+    verdict, status, _, _ = apply_update_batch(ctx, [(msa_before, update)], [msa_claimed])[0]
+    return verdict, status
+
+
+def accumulator_after(ctx, msa, guesser_fee_addition_records):
+    """`Block::mutator_set_accumulator_after` (mod.rs:369-378): `msa` with the guesser-fee addition records
+    applied, an update with additions only.  Raises when `msa` is inconsistent."""
+    from .mutator_set import MutatorSetUpdate, apply_update_batch
+    verdict, status, _, after = apply_update_batch(ctx, [(msa, MutatorSetUpdate((), list(guesser_fee_addition_records)))])[0]
+    if not verdict:
+        raise ValueError(f"mutator set accumulator rejected: status {status}")
+    return after
+
+
 @dataclass
 class TransferTransaction:
     """transfer_transaction.rs:31-47: `kernel_sequences` (the kernel's 8 MAST sequences) and the

@@ -9,6 +9,11 @@ consensus step after "the proof verifies", batched.
 * `verify_batch(ctx, msa, items, proofs)` — `MutatorSetAccumulator::verify`
   (mutator_set_accumulator.rs:252-339): state/wallet/wallet_state.rs:1796,1958.
 
+* `apply_update_batch(ctx, jobs, expected=None)` — `Block::validate` rules 2.b-2.e
+  (protocol/consensus/block/mod.rs:816-849) and `Block::mutator_set_accumulator_after`
+  (mod.rs:369-378) for many independent `(msa_before, MutatorSetUpdate)` jobs: the accumulator after
+  each update, computed on the device.
+
 The types mirror the reference's over numpy; every verdict is the device's.  Where the reference
 would panic or truncate (an index past the active window, or >= 2^76) the record is rejected with
 `OUT_OF_RANGE`.
@@ -28,7 +33,9 @@ from .mast import NUM_TRIALS, AbsoluteIndexSet
 CHUNK_SIZE = 1 << 12
 BATCH_SIZE = 1 << 3
 OK, ABSENT_CHUNK, BAD_MMR_PATH, ALREADY_REMOVED, OUT_OF_RANGE, NOT_IN_AOCL = range(6)
-STATUS_NAMES = ("OK", "ABSENT_CHUNK", "BAD_MMR_PATH", "ALREADY_REMOVED", "OUT_OF_RANGE", "NOT_IN_AOCL")
+INCONSISTENT, DUPLICATE_RECORD, UPDATE_IMPOSSIBLE, UPDATE_MISMATCH = range(6, 10)  # apply_update_batch only
+STATUS_NAMES = ("OK", "ABSENT_CHUNK", "BAD_MMR_PATH", "ALREADY_REMOVED", "OUT_OF_RANGE", "NOT_IN_AOCL",
+                "INCONSISTENT", "DUPLICATE_RECORD", "UPDATE_IMPOSSIBLE", "UPDATE_MISMATCH")
 
 
 def _digests(x, n=None) -> np.ndarray:
@@ -205,3 +212,98 @@ def verify_batch(ctx, msa: MutatorSetAccumulator, items, proofs: Sequence[MsMemb
                                        leaf.ctypes.data, off.ctypes.data, _ptr(path), ctypes.byref(cc), n,
                                        v.ctypes.data, status.ctypes.data), "nhip_ms_verify_batch")
     return [(bool(v[i]), int(status[i])) for i in range(n)]
+
+
+@dataclass
+class MutatorSetUpdate:
+    """block/mutator_set_update.rs:14-21: the removal records of a block in block order, and its addition
+    records (each an `AdditionRecord::canonical_commitment` digest)."""
+    removals: Sequence[RemovalRecord] = ()
+    additions: Sequence[Sequence[int]] = ()
+
+
+def _index_arrays(records):
+    n = len(records)
+    mn = np.zeros((n, 2), dtype=np.uint64)
+    dist = np.zeros((n, NUM_TRIALS), dtype=np.uint32)
+    for i, r in enumerate(records):
+        m = int(r.absolute_indices.minimum)
+        mn[i] = (m & (2 ** 64 - 1), m >> 64)
+        dist[i] = np.asarray(r.absolute_indices.distances, dtype=np.uint32)
+    return mn, dist
+
+
+def _csr(counts) -> np.ndarray:
+    off = np.zeros(len(counts) + 1, dtype=np.uint64)
+    if len(counts):
+        off[1:] = np.cumsum(counts, dtype=np.uint64)
+    return off
+
+
+class PackedApply:
+    """The arguments of one `nhip_ms_apply_batch` call over numpy arrays: `cin` / `cout` are the C structs,
+    `arrays` keeps every array they point into alive (and lets a caller read the outputs)."""
+
+    def __init__(self, jobs, expected=None):
+        n = self.n = len(jobs)
+        if expected is not None and len(expected) != n:
+            raise ValueError("one expected accumulator per job")
+        self._keep = []
+        self.before = (_lib.Msa * max(n, 1))()
+        for j, (msa, _) in enumerate(jobs):
+            self.before[j], k = msa._c()
+            self._keep.append(k)
+        self.expected = None
+        if expected is not None:
+            self.expected = (_lib.Msa * max(n, 1))()
+            for j, msa in enumerate(expected):
+                self.expected[j], k = msa._c()
+                self._keep.append(k)
+        adds = [d for _, u in jobs for d in u.additions]
+        records = [r for _, u in jobs for r in u.removals]
+        mn, dist = _index_arrays(records)
+        self.packed = pack_chunks(records)
+        self.chunks = self.packed._c()
+        z = lambda dtype, *shape: np.zeros(shape, dtype=dtype)  # noqa: E731
+        self.arrays = a = dict(
+            additions=_digests(adds) if adds else z(np.uint64, 0, 5),
+            add_off=_csr([len(u.additions) for _, u in jobs]), rec_off=_csr([len(u.removals) for _, u in jobs]),
+            minimum=mn, distances=dist, verdict=z(np.uint8, n), status=z(np.uint8, n), bad_record=z(np.uint64, n),
+            aocl_peaks=z(np.uint64, n, 64, 5), aocl_n_peaks=z(np.uint32, n), aocl_num_leafs=z(np.uint64, n),
+            swbf_peaks=z(np.uint64, n, 64, 5), swbf_n_peaks=z(np.uint32, n), swbf_num_leafs=z(np.uint64, n),
+            active_off=_csr([len(msa.swbf_active) + NUM_TRIALS * len(u.removals) for msa, u in jobs]),
+            n_active=z(np.uint64, n))
+        a["active"] = z(np.uint32, max(int(a["active_off"][-1]), 1))
+        self.cin = _lib.MsApplyIn(n, self.before, a["add_off"].ctypes.data, _ptr(a["additions"]),
+                                  a["rec_off"].ctypes.data, _ptr(mn), _ptr(dist), ctypes.pointer(self.chunks),
+                                  self.expected)
+        self.cout = _lib.MsApplyOut(*(a[f].ctypes.data for f, _ in _lib.MsApplyOut._fields_))
+
+    def call(self, ctx) -> int:
+        return ctx.lib.nhip_ms_apply_batch(ctx.handle, ctypes.byref(self.cin), ctypes.byref(self.cout))
+
+
+def apply_update_batch(ctx, jobs, expected=None):
+    """`jobs`: `(MutatorSetAccumulator before, MutatorSetUpdate)` pairs, independent of each other;
+    `expected`: one `MutatorSetAccumulator` per job, or None.  Per job `(verdict, status, bad_record,
+    msa_after)`: `bad_record` is the position in the job's removals of the record the status blames
+    (None when it blames none), and `msa_after` is the accumulator after the update when the status is
+    OK or UPDATE_MISMATCH, else None.  The steps and their order are those of `nhip_ms_apply_batch`."""
+    n = len(jobs)
+    if n == 0:
+        return []
+    pa = PackedApply(jobs, expected)
+    check(pa.call(ctx), "nhip_ms_apply_batch")
+    a = pa.arrays
+    out = []
+    for j in range(n):
+        after = None
+        status = int(a["status"][j])
+        if status in (OK, UPDATE_MISMATCH):
+            mmrs = [MmrAccumulator([tuple(int(x) for x in d) for d in a[w + "_peaks"][j, :int(a[w + "_n_peaks"][j])]],
+                                   int(a[w + "_num_leafs"][j])) for w in ("aocl", "swbf")]
+            lo = int(a["active_off"][j])
+            after = MutatorSetAccumulator(mmrs[0], mmrs[1], [int(x) for x in a["active"][lo:lo + int(a["n_active"][j])]])
+        bad = int(a["bad_record"][j])
+        out.append((bool(a["verdict"][j]), status, None if bad == 2 ** 64 - 1 else bad, after))
+    return out

@@ -204,6 +204,43 @@ pub const NHIP_MS_BAD_MMR_PATH: u8 = 2;
 pub const NHIP_MS_ALREADY_REMOVED: u8 = 3;
 pub const NHIP_MS_OUT_OF_RANGE: u8 = 4;
 pub const NHIP_MS_NOT_IN_AOCL: u8 = 5;
+pub const NHIP_MS_INCONSISTENT: u8 = 6;
+pub const NHIP_MS_DUPLICATE_RECORD: u8 = 7;
+pub const NHIP_MS_UPDATE_IMPOSSIBLE: u8 = 8;
+pub const NHIP_MS_UPDATE_MISMATCH: u8 = 9;
+
+/// The jobs of one `nhip_ms_apply_batch` call (CSR over the jobs; `msa_expected` may be null).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_ms_apply_in {
+    pub n_jobs: usize,
+    pub msa_before: *const nhip_msa,
+    pub add_off: *const u64,
+    pub additions: *const u64,
+    pub rec_off: *const u64,
+    pub minimum: *const u64,
+    pub distances: *const u32,
+    pub chunks: *const nhip_ms_chunks,
+    pub msa_expected: *const nhip_msa,
+}
+
+/// Per-job verdicts and, when every accumulator pointer is given, the accumulators after.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_ms_apply_out {
+    pub verdict: *mut u8,
+    pub status: *mut u8,
+    pub bad_record: *mut u64,
+    pub aocl_peaks: *mut u64,
+    pub aocl_n_peaks: *mut u32,
+    pub aocl_num_leafs: *mut u64,
+    pub swbf_peaks: *mut u64,
+    pub swbf_n_peaks: *mut u32,
+    pub swbf_num_leafs: *mut u64,
+    pub active_off: *const u64,
+    pub active: *mut u32,
+    pub n_active: *mut u64,
+}
 
 extern "C" {
     pub fn nhip_init(device_mask: u32, out: *mut *mut nhip_ctx) -> c_int;
@@ -391,6 +428,8 @@ extern "C" {
                                 aocl_leaf_index: *const u64, aocl_path_off: *const u64, aocl_path: *const u64,
                                 chunks: *const nhip_ms_chunks, n: usize, verdicts: *mut u8,
                                 status: *mut u8) -> c_int;
+    pub fn nhip_ms_apply_batch(ctx: *mut nhip_ctx, input: *const nhip_ms_apply_in,
+                               out: *mut nhip_ms_apply_out) -> c_int;
     pub fn nhip_timing_enable(ctx: *mut nhip_ctx, on: c_int) -> c_int;
     pub fn nhip_timing_read(ctx: *mut nhip_ctx, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
 }
