@@ -198,6 +198,11 @@ int nhip_air_slots(const nhip_air *air, uint32_t *lds_slots, uint32_t *global_sl
  * small capacities) just report the sizes; NHIP_ERR_ARG when a given array is too small. */
 int nhip_air_program(const nhip_air *air, uint32_t *step_off, size_t step_cap, uint32_t *ins, size_t ins_cap,
                      size_t *n_steps, size_t *n_ins);
+/* The per-kind segments of that program's steps (host only): 3 bounds per step, of its copies (LOAD /
+ * ACC), its products and its sums and differences, then the end of the program: 3 * steps + 1 offsets,
+ * seg_off[3 s] == step_off[s].  k_ood_air runs a step segment by segment, each from its thread 0, so
+ * a wave runs one kind of operation.  A NULL array just reports the count. */
+int nhip_air_segments(const nhip_air *air, uint32_t *seg_off, size_t seg_cap, size_t *n_bounds);
 /* Host-only structural decode (no GPU needed): 1 = decodes, 0 = malformed, < 0 = bad argument. */
 int nhip_proof_decodes(const nhip_air *air, const nhip_stark_params *params, const nhip_claim *claim,
                        const nhip_proof *proof);

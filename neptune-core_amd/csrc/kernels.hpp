@@ -218,7 +218,7 @@ struct StarkBatchDev {
     MpPlan mp;
     const uint64_t* mp_cap_host;  // host: op capacity per level (launch sizes)
     const OodIns* air_prog;        // compiled AIR (OodIns per level)
-    const uint32_t* air_prog_off;  // [n_levels + 1]
+    const uint32_t* air_prog_off;  // [3 n_levels + 1]: the steps' per-kind segment bounds (seg_off)
     uint32_t air_n_levels;
     const Xfe* air_consts;         // constant table (raw Montgomery)
     uint4 air_cons_off;            // constraint-type boundaries

@@ -125,6 +125,9 @@ PinnedRanges& pinned() {
 struct OodProgram {
     std::vector<OodIns> prog;
     std::vector<uint32_t> prog_off;
+    // per-kind segments of each step (copies, products, sums and differences): 3 bounds per step + the
+    // end, seg_off[3 s] == prog_off[s]; k_ood_air runs one loop per segment, so a wave runs one kind
+    std::vector<uint32_t> seg_off;
     std::vector<Xfe> consts;
     uint32_t slots = 0;
     uint32_t width = 0;
@@ -148,7 +151,7 @@ struct nhip_air {
     struct Dev {
         int device;
         OodIns* d_prog[2];
-        uint32_t* d_prog_off[2];
+        uint32_t* d_prog_off[2];  // the segment bounds (OodProgram::seg_off)
         Xfe* d_consts[2];
     };
     std::mutex mu;
@@ -289,12 +292,12 @@ int air_upload(nhip_ctx* ctx, nhip_air* a, nhip_air::Dev* out) {
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
         const OodProgram& pg = a->progs[k];
         e = hipMalloc(&d.d_prog[k], pg.prog.size() * sizeof(OodIns) + 16);
-        if (e == hipSuccess) e = hipMalloc(&d.d_prog_off[k], pg.prog_off.size() * 4 + 4);
+        if (e == hipSuccess) e = hipMalloc(&d.d_prog_off[k], pg.seg_off.size() * 4 + 4);
         if (e == hipSuccess) e = hipMalloc(&d.d_consts[k], pg.consts.size() * sizeof(Xfe) + 24);
         if (e == hipSuccess && !pg.prog.empty())
             e = hipMemcpy(d.d_prog[k], pg.prog.data(), pg.prog.size() * sizeof(OodIns), hipMemcpyHostToDevice);
         if (e == hipSuccess)
-            e = hipMemcpy(d.d_prog_off[k], pg.prog_off.data(), pg.prog_off.size() * 4, hipMemcpyHostToDevice);
+            e = hipMemcpy(d.d_prog_off[k], pg.seg_off.data(), pg.seg_off.size() * 4, hipMemcpyHostToDevice);
         if (e == hipSuccess && !pg.consts.empty())
             e = hipMemcpy(d.d_consts[k], pg.consts.data(), pg.consts.size() * sizeof(Xfe), hipMemcpyHostToDevice);
     }
@@ -316,6 +319,8 @@ int air_upload(nhip_ctx* ctx, nhip_air* a, nhip_air::Dev* out) {
 // Instructions per step of the compiled AIR program: two per thread of k_ood_air's 256-thread
 // workgroups (nhip_air_options.step_width sets another, tests of the compiler).
 static constexpr uint32_t OOD_STEP_WIDTH = 512;
+// Products of a step come in multiples of a wave where the ready list allows (air_compile).
+static constexpr uint32_t OOD_MUL_QUOTA = 64;
 
 // The program a batch of n proofs runs: the wide-step one up to NHIP_OOD_WIDE_PROG_MAX proofs (default
 // 1,024), where one proof's evaluation latency matters more than proofs per CU.  Config 4 per-GPU
@@ -448,6 +453,43 @@ void air_compile(const nhip_air* a, const std::vector<uint32_t>& cons, uint32_t 
                 rest.push_back(i);
             }
         }
+        // Products in whole waves: a 64-lane pass of k_ood_air that holds one product pays an XFE
+        // product on the whole wave, so the products past the last multiple of 64 (the step's lowest
+        // priorities among them) wait for a later step, where they fill a wave with the products that
+        // have become ready by then, unless that would leave the step empty or they retire a value
+        // (waiting would hold the slot).  Ready sums, differences and copies take the room.
+        {
+            const auto is_mul = [&](uint32_t i) { return a->nodes[i].op == AIR_MUL; };
+            size_t muls = 0;
+            for (uint32_t i : chosen) muls += is_mul(i);
+            size_t drop = muls % OOD_MUL_QUOTA;
+            if (drop && (muls > drop || chosen.size() > muls)) {
+                std::vector<uint32_t> kept, back;
+                for (size_t k = chosen.size(); k-- > 0;) {
+                    const uint32_t i = chosen[k];
+                    if (drop && is_mul(i) && key[i].first == 0) {
+                        back.push_back(i);
+                        --drop;
+                        --live;
+                    } else {
+                        kept.push_back(i);
+                    }
+                }
+                std::reverse(kept.begin(), kept.end());
+                chosen.swap(kept);
+                std::vector<uint32_t> rest2;
+                for (uint32_t i : rest) {
+                    if (!is_mul(i) && chosen.size() < room && (live < budget || key[i].first < 0)) {
+                        chosen.push_back(i);
+                        ++live;
+                    } else {
+                        rest2.push_back(i);
+                    }
+                }
+                rest.swap(rest2);
+                rest.insert(rest.end(), back.begin(), back.end());
+            }
+        }
         ready.swap(rest);
         for (uint32_t i : chosen) {
             uint32_t sl;
@@ -482,10 +524,17 @@ void air_compile(const nhip_air* a, const std::vector<uint32_t>& cons, uint32_t 
         };
         std::stable_sort(cur.begin(), cur.end(),
                          [&](const OodIns& x, const OodIns& y) { return kind_rank(x.op) < kind_rank(y.op); });
+        // the bounds of the step's segments: copies | products | sums and differences
+        uint32_t bound = (uint32_t)pg.prog.size();
+        for (int rank = 0; rank < 3; ++rank) {
+            pg.seg_off.push_back(bound);
+            for (const OodIns& ins : cur) bound += kind_rank(ins.op) == rank || (rank == 2 && kind_rank(ins.op) == 3);
+        }
         pg.prog.insert(pg.prog.end(), cur.begin(), cur.end());
         pg.prog_off.push_back((uint32_t)pg.prog.size());
         cur.clear();
     }
+    pg.seg_off.push_back((uint32_t)pg.prog.size());
     for (OodIns& ins : pg.prog)
         if (ins.op == OOD_ACC) ins.dst = next_slot + ins.b;
     pg.slots = next_slot + (uint32_t)cons.size();
@@ -643,6 +692,19 @@ int nhip_air_program(const nhip_air* a, uint32_t* step_off, size_t step_cap, uin
             ins[4 * i + 2] = pg.prog[i].b;
             ins[4 * i + 3] = pg.prog[i].dst;
         }
+    }
+    return NHIP_OK;
+}
+
+// The per-kind segments of the program's steps: 3 bounds per step (copies, products, sums and
+// differences) and the end of the program.
+int nhip_air_segments(const nhip_air* a, uint32_t* seg_off, size_t seg_cap, size_t* n_bounds) {
+    if (!a) return NHIP_ERR_ARG;
+    const OodProgram& pg = a->progs[0];
+    if (n_bounds) *n_bounds = pg.seg_off.size();
+    if (seg_off) {
+        if (seg_cap < pg.seg_off.size()) return NHIP_ERR_ARG;
+        std::memcpy(seg_off, pg.seg_off.data(), pg.seg_off.size() * 4);
     }
     return NHIP_OK;
 }

@@ -1170,21 +1170,36 @@ __device__ __forceinline__ Xfe shfl_xor_xfe(Xfe v, int m) {
             (uint64_t)__shfl_xor((long long)v.c2, m)};
 }
 
-// EvalArg::compute_terminal(symbols[0..n), initial 1, c) on one full wave: lane j folds the chunk
-// [j ch, (j + 1) ch) by Horner, scales it by c^(n - chunk end), and the wave sums the chunks plus
-// c^n (the initial 1).  Same value as the sequential fold; n / 64 + ~2 log2 n products per lane.
+// EvalArg::compute_terminal(symbols[0..n), initial 1, c) on one wave, every step wave-uniform.  The
+// fold from 1 is Horner from 0 over [1, symbols...]; that sequence, zero-padded in front to L * ch
+// entries (L = 2^s lanes, the smallest power of two >= min(64, n + 1); ch = ceil((n + 1) / L)), is
+// split into L chunks: lane j folds chunk j by Horner while c^ch is formed beside it, and s shuffle
+// steps join neighbouring groups, value = low group * c^(ch 2^k) + high group, the multiplier squared
+// from step to step.  Same value as the sequential fold (c^n comes out of the chain with the leading
+// 1); 2 (ch - 1) + 2 s - 1 products on the wave, no per-lane exponent.  Lanes below L hold the result.
 template <class Sym>
 __device__ Xfe eval_terminal_wave(uint32_t n, Xfe c, Sym sym) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t ch = (n + 63u) / 64u;
-    const uint32_t lo = min(n, lane * ch), hi = min(n, lo + ch);
-    Xfe h = x_zero();
-    for (uint32_t i = lo; i < hi; ++i) h = x_add(x_mul(h, c), x_lift(sym(i)));
-    Xfe t = hi > lo ? x_mul(h, x_pow(c, n - hi)) : x_zero();
-    if (lane == 0) t = x_add(t, x_pow(c, n));
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) t = x_add(t, shfl_xor_xfe(t, m));
-    return t;
+    uint32_t s = 0;
+    while (s < 6u && (1u << s) < n + 1u) ++s;
+    const uint32_t L = 1u << s, ch = (n + L) >> s, pad = L * ch - n;  // entry pad - 1 is the leading 1
+    auto entry = [&](uint32_t pos) -> Xfe {
+        if (lane >= L) return x_zero();
+        if (pos >= pad) return x_lift(sym(pos - pad));  // pos < L ch, so pos - pad < n
+        return pos + 1u == pad ? x_one() : x_zero();
+    };
+    Xfe h = entry(lane * ch), m = c;
+    for (uint32_t k = 1; k < ch; ++k) {
+        h = x_add(x_mul(h, c), entry(lane * ch + k));
+        m = x_mul(m, c);
+    }
+    for (uint32_t k = 0; k < s; ++k) {
+        const Xfe o = shfl_xor_xfe(h, 1 << k);
+        const bool up = (lane >> k) & 1u;
+        h = x_add(x_mul(up ? o : h, m), up ? h : o);
+        if (k + 1u < s) m = x_mul(m, m);
+    }
+    return h;
 }
 
 // ------------------------------------------------------------------ OOD: AIR + quotient identity
@@ -1205,7 +1220,7 @@ __device__ Xfe eval_terminal_wave(uint32_t n, Xfe c, Sym sym) {
 template <uint32_t BLOCK, bool MW, bool GS>
 __global__ void __launch_bounds__(BLOCK, BLOCK == 256 ? NHIP_OOD_WAVES : 1) k_ood_air(const uint64_t* __restrict__ words, const ProofDesc* __restrict__ desc,
                                                  uint32_t n_proofs, StarkDims dims, const OodIns* __restrict__ prog,
-                                                 const uint32_t* __restrict__ prog_off, uint32_t n_levels,
+                                                 const uint32_t* __restrict__ seg_off, uint32_t n_levels,
                                                  const Xfe* __restrict__ consts, uint4 cons_type_off,
                                                  const uint64_t* __restrict__ xs, uint64_t* __restrict__ ood_out,
                                                  uint32_t* __restrict__ fail, uint32_t lds_slots,
@@ -1216,7 +1231,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 256 ? NHIP_OOD_WAVES : 1) k_oo
     Xfe* red = reinterpret_cast<Xfe*>(smem);              // 16 (one per wave)
     Xfe* zinv = red + 16;                                  // 4
     Xfe* chal_derived = zinv + 4;                          // 4 (Challenges::new)
-    Xfe* misc = chal_derived + 4;                          // 4 (1 used: z - w^-1)
+    Xfe* misc = chal_derived + 4;                          // 4 (spare)
     uint32_t& zero_flag = *reinterpret_cast<uint32_t*>(misc + 4);
     Xfe* val = reinterpret_cast<Xfe*>(smem + AIR_LDS_HEADER);
     const uint32_t p = blockIdx.x, tid = threadIdx.x;
@@ -1236,47 +1251,54 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 256 ? NHIP_OOD_WAVES : 1) k_oo
     const Xfe z = ld_xfe_raw(xs, xb + 3ull * sl.z);
     if (tid == 0) zero_flag = 0;
     __syncthreads();
-    // zerofier inverses (triton-vm verify: initial, consistency, transition, terminal), one
-    // inversion per wave, and the derived challenges
+    // zerofier inverses (triton-vm verify: initial, consistency, transition, terminal) on wave 0:
+    // one inversion for the three (Montgomery's trick; a zero zerofier is flagged, stands in the
+    // product as 1 and gets the inverse 0, as x_inv gives it), and the derived challenges on waves 1-3
     if (tid == 0) {
         const uint64_t w_inv = b_inv(root_of_unity(d.log2_ph));
         const Xfe except_last = x_sub(z, x_lift(w_inv));
-        if (x_is_zero(except_last)) atomicOr(&zero_flag, 1u);
-        misc[0] = except_last;
-        zinv[3] = x_inv(except_last);
-    } else if (tid == 64) {
         const Xfe zm1 = x_sub(z, x_one());
-        if (x_is_zero(zm1)) atomicOr(&zero_flag, 1u);
-        zinv[0] = x_inv(zm1);
-    } else if (tid == 128) {
         Xfe zph = z;
         for (uint32_t q = 0; q < d.log2_ph; ++q) zph = x_mul(zph, zph);
         const Xfe cons = x_sub(zph, x_one());
-        if (x_is_zero(cons)) atomicOr(&zero_flag, 1u);
-        zinv[1] = x_inv(cons);
-    } else if (tid >= 192 && tid < 256) {
+        const bool z0 = x_is_zero(zm1), z1 = x_is_zero(cons), z3 = x_is_zero(except_last);
+        if (z0 || z1 || z3) zero_flag = 1u;
+        const Xfe a = z0 ? x_one() : zm1, b = z1 ? x_one() : cons, c = z3 ? x_one() : except_last;
+        const Xfe ab = x_mul(a, b);
+        const Xfe iabc = x_inv(x_mul(ab, c));
+        const Xfe iab = x_mul(iabc, c);
+        const Xfe i1 = z1 ? x_zero() : x_mul(iab, a);
+        zinv[0] = z0 ? x_zero() : x_mul(iab, b);
+        zinv[1] = i1;
+        zinv[2] = x_mul(except_last, i1);
+        zinv[3] = z3 ? x_zero() : x_mul(iabc, ab);
+    } else if (tid >= 64 && tid < 256) {
         // Challenges::new: the 4 derived challenges in ChallengeId order, each an EvalArg terminal
-        // folded from 1 with its named sampled indeterminate (wave 3, lane-parallel)
+        // folded from 1 with its named sampled indeterminate, a wave each (the program digest's
+        // short fold behind the input's)
         auto chal = [&](uint32_t i) { return ld_xfe_raw(xs, xb + 3ull * (sl.chal + i)); };
-        const Xfe ein = eval_terminal_wave(d.claim_in_n, chal(CH_STANDARD_INPUT),
-                                           [&](uint32_t i) { return word_mont<MW>(words[d.claim_in_off + i]); });
-        const Xfe eout = eval_terminal_wave(d.claim_out_n, chal(CH_STANDARD_OUTPUT),
-                                            [&](uint32_t i) { return word_mont<MW>(words[d.claim_out_off + i]); });
-        const Xfe lut = eval_terminal_wave(256u, chal(CH_LOOKUP_TABLE_PUBLIC), [&](uint32_t i) {
-            const uint64_t y = i + 1;  // tip5::LOOKUP_TABLE[i] = (i + 1)^3 - 1 mod 257
-            return to_mont((y * y % 257u * y % 257u + 256u) % 257u);
-        });
-        const Xfe comp = eval_terminal_wave(5u, chal(CH_COMPRESS_PROGRAM_DIGEST),
-                                            [&](uint32_t i) { return word_mont<MW>(words[d.claim_digest_off + i]); });
-        if (tid == 192) {
-            chal_derived[0] = ein;
-            chal_derived[1] = eout;
-            chal_derived[2] = lut;
-            chal_derived[3] = comp;
+        const uint32_t wv = tid >> 6;
+        if (wv == 1) {
+            const Xfe lut = eval_terminal_wave(256u, chal(CH_LOOKUP_TABLE_PUBLIC), [&](uint32_t i) {
+                const uint64_t y = i + 1;  // tip5::LOOKUP_TABLE[i] = (i + 1)^3 - 1 mod 257
+                return to_mont((y * y % 257u * y % 257u + 256u) % 257u);
+            });
+            if (tid == 64) chal_derived[2] = lut;
+        } else if (wv == 2) {
+            const Xfe ein = eval_terminal_wave(d.claim_in_n, chal(CH_STANDARD_INPUT),
+                                               [&](uint32_t i) { return word_mont<MW>(words[d.claim_in_off + i]); });
+            const Xfe comp = eval_terminal_wave(5u, chal(CH_COMPRESS_PROGRAM_DIGEST),
+                                                [&](uint32_t i) { return word_mont<MW>(words[d.claim_digest_off + i]); });
+            if (tid == 128) {
+                chal_derived[0] = ein;
+                chal_derived[3] = comp;
+            }
+        } else {
+            const Xfe eout = eval_terminal_wave(d.claim_out_n, chal(CH_STANDARD_OUTPUT),
+                                                [&](uint32_t i) { return word_mont<MW>(words[d.claim_out_off + i]); });
+            if (tid == 192) chal_derived[1] = eout;
         }
     }
-    __syncthreads();
-    if (tid == 0) zinv[2] = x_mul(misc[0], zinv[1]);
     __syncthreads();
     const uint32_t offs[5] = {0u, cons_type_off.x, cons_type_off.y, cons_type_off.z, cons_type_off.w};
     auto fetch = [&](uint32_t ref) -> Xfe {
@@ -1297,16 +1319,25 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 256 ? NHIP_OOD_WAVES : 1) k_oo
     // between steps).  Batching a thread's instructions of a step (all operands requested first)
     // and loading the next step's instruction words during the current one measured slower: config
     // 4 -1.3% at 4,096 proofs, -1% at 512 (profiles/r04e), so each instruction runs on its own.
+    // A step runs segment by segment (seg_off: its copies, its products, its sums and differences),
+    // each from thread 0: a wave-iteration runs one kind of XFE operation, chosen by the segment and
+    // not per lane, and a step's products fill ceil(products / 64) waves.
     for (uint32_t lvl = 0; lvl < n_levels; ++lvl) {
-        for (uint32_t q = prog_off[lvl] + tid; q < prog_off[lvl + 1]; q += blockDim.x) {
+        const uint32_t s0 = seg_off[3 * lvl], s1 = seg_off[3 * lvl + 1], s2 = seg_off[3 * lvl + 2],
+                       s3 = seg_off[3 * lvl + 3];
+        for (uint32_t q = s0 + tid; q < s1; q += blockDim.x) {
             const uint4 ins = reinterpret_cast<const uint4*>(prog)[q];  // (op, a, b, dst): one 16-B load
-            if (ins.x >= OOD_LOAD) {  // an input into its slot, or a constraint into its own slot
-                slot_st(ins.w, fetch(ins.y));
-            } else {
-                // operands are slots (air_compile copies inputs and constants into slots first)
-                const Xfe x = slot_ld(ins.y), y = slot_ld(ins.z);
-                slot_st(ins.w, ins.x == OOD_ADD ? x_add(x, y) : (ins.x == OOD_SUB ? x_sub(x, y) : x_mul(x, y)));
-            }
+            slot_st(ins.w, fetch(ins.y));  // an input into its slot, or a constraint into its own slot
+        }
+        // operands are slots (air_compile copies inputs and constants into slots first)
+        for (uint32_t q = s1 + tid; q < s2; q += blockDim.x) {
+            const uint4 ins = reinterpret_cast<const uint4*>(prog)[q];
+            slot_st(ins.w, x_mul(slot_ld(ins.y), slot_ld(ins.z)));
+        }
+        for (uint32_t q = s2 + tid; q < s3; q += blockDim.x) {
+            const uint4 ins = reinterpret_cast<const uint4*>(prog)[q];
+            const Xfe x = slot_ld(ins.y), y = slot_ld(ins.z);
+            slot_st(ins.w, ins.x == OOD_ADD ? x_add(x, y) : x_sub(x, y));  // both cheap: per lane
         }
         __syncthreads();
     }
@@ -1332,14 +1363,29 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 256 ? NHIP_OOD_WAVES : 1) k_oo
     }
     const Xfe sum_c = block_sum_xfe_waves(lc, red);
     const Xfe sum_n = block_sum_xfe_waves(ln, red);
-    if (tid == 0) {
-        Xfe seg = x_zero(), zk = x_one(), qlin = x_zero();
-        for (uint32_t q = 0; q < Q; ++q) {
+    if (tid >= 64) return;
+    // sum_q z^q * segment_q(z^4) and the segments' linear combination on wave 0, a segment per lane:
+    // z^q from the bits of q over the squarings of z (wave-uniform), then two wave sums
+    Xfe seg = x_zero(), qlin = x_zero();
+    for (uint32_t base = 0; base < Q; base += 64u) {
+        const uint32_t q = base + tid, top = min(Q - 1u, base + 63u);  // top: the largest exponent here
+        Xfe zk = (q & 1u) ? z : x_one(), zp = z;
+        for (uint32_t e = top >> 1, bit = 1; e; e >>= 1, ++bit) {
+            zp = x_mul(zp, zp);
+            zk = x_mul(zk, ((q >> bit) & 1u) ? zp : x_one());
+        }
+        if (q < Q) {
             const Xfe sq = ld_xfe_w<MW>(words, d.ood_qs + 3ull * q);
             seg = x_add(seg, x_mul(zk, sq));
-            zk = x_mul(zk, z);
             qlin = x_add(qlin, x_mul(ld_xfe_raw(xs, xb + 3ull * (sl.lin_w + M + A + q)), sq));
         }
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        seg = x_add(seg, shfl_xor_xfe(seg, m));
+        qlin = x_add(qlin, shfl_xor_xfe(qlin, m));
+    }
+    if (tid == 0) {
         uint32_t f = 0;
         if (zero_flag) f |= FAIL_ZERO_INVERSE;
         if (!x_eq(seg, ood_q)) f |= FAIL_OOD;

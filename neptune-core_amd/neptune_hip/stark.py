@@ -133,6 +133,16 @@ class Air:
                                         ctypes.byref(ns), ctypes.byref(ni)), "nhip_air_program")
         return off, ins[:ni.value]
 
+    def segments(self):
+        """The per-kind segments of the program's steps (nhip_air_segments): an (steps, 4) array of
+        bounds, row s = [copies | products | sums and differences | end of step s]."""
+        n = ctypes.c_size_t()
+        check(self.lib.nhip_air_segments(self.handle, None, 0, ctypes.byref(n)), "nhip_air_segments")
+        seg = np.zeros(n.value, dtype=np.uint32)
+        check(self.lib.nhip_air_segments(self.handle, seg.ctypes.data, seg.size, ctypes.byref(n)), "nhip_air_segments")
+        steps = (n.value - 1) // 3
+        return np.stack([seg[k:k + 3 * steps:3] for k in range(3)] + [seg[3::3]], axis=1)
+
     def __del__(self):
         try:
             if self.handle:

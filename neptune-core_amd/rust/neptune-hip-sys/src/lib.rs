@@ -280,6 +280,7 @@ extern "C" {
                          num_constraints: *mut u32) -> c_int;
     pub fn nhip_air_program(air: *const nhip_air, step_off: *mut u32, step_cap: usize, ins: *mut u32, ins_cap: usize,
                             n_steps: *mut usize, n_ins: *mut usize) -> c_int;
+    pub fn nhip_air_segments(air: *const nhip_air, seg_off: *mut u32, seg_cap: usize, n_bounds: *mut usize) -> c_int;
     pub fn nhip_air_slots(air: *const nhip_air, lds_slots: *mut u32, global_slots: *mut u32) -> c_int;
     pub fn nhip_proof_decodes(air: *const nhip_air, params: *const nhip_stark_params,
                               claim: *const nhip_claim, proof: *const nhip_proof) -> c_int;
