@@ -1,9 +1,6 @@
-// C-ABI layer of libneptune_hip.so (declarations: include/neptune_hip.h).
-//
-// One nhip_ctx = one GPU, one non-blocking HIP stream, a grow-only device workspace for the
-// host-buffer entry points, and an optional event timer around every kernel launch.  Calls on
-// one context are serialized by a mutex (the reference calls verify() concurrently from many
-// tokio tasks: neptune-core/src/protocol/proof_abstractions/verifier.rs:60-63).
+// C-ABI layer of libneptune_hip.so (declarations: include/neptune_hip.h): the context (ctx.hpp), the
+// device-resident and host-buffer hashing calls, wire bytes -> words, timing.  The mutator-set entry
+// points are ms_capi.hip's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,100 +9,17 @@
 #include <new>
 #include <vector>
 
-#include "../../include/neptune_hip.h"
+#include "ctx.hpp"
 #include "device_scope.hpp"
-#include "host_numa.hpp"
 #include "kernels.hpp"
 #include "ms_shape.hpp"
 #include "wire.hpp"
 
-struct nhip_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::mutex mu;
-    void* ws = nullptr;  // workspace for host-buffer calls
-    size_t ws_bytes = 0;
-    void* staging = nullptr;  // pinned host staging for batch uploads (grow-only, under mu)
-    size_t staging_bytes = 0;
-    void* verify_scratch = nullptr;  // reusable device / stream resources of nhip_verify_batch
-    void (*verify_scratch_free)(void*) = nullptr;
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;  // recorded, not yet read
-    std::vector<hipEvent_t> free_events;
-    double timed_ms = 0.0;
-    uint64_t timed_launches = 0;
-    nhip::HostTopo topo;       // the GPU's NUMA node and its CPUs (host_numa.cpp)
-    unsigned host_threads = 0;  // staging copy threads per upload (0: the default)
-};
+using nhip::hip_fail;
+using nhip::Stage;
+using nhip::timed_launch;
 
 namespace {
-
-int hip_fail(hipError_t e) {
-    if (e == hipSuccess) return NHIP_OK;
-    if (e == hipErrorOutOfMemory) return NHIP_ERR_OOM;
-    return NHIP_ERR_HIP;
-}
-
-hipEvent_t take_event(nhip_ctx* c) {
-    if (!c->free_events.empty()) {
-        hipEvent_t e = c->free_events.back();
-        c->free_events.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
-
-// Launch helper: brackets the launch with events when timing is on.
-template <class F>
-int timed_launch(nhip_ctx* c, F&& f) {
-    hipEvent_t a = nullptr, b = nullptr;
-    if (c->timing) {
-        a = take_event(c);
-        b = take_event(c);
-        if (a && b) (void)hipEventRecord(a, c->stream);
-    }
-    hipError_t e = f();
-    if (c->timing && a && b) {
-        (void)hipEventRecord(b, c->stream);
-        c->pending.emplace_back(a, b);
-    }
-    return hip_fail(e);
-}
-
-int ensure_ws(nhip_ctx* c, size_t bytes) {
-    if (bytes <= c->ws_bytes) return NHIP_OK;
-    if (c->ws) {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(c->ws);
-        c->ws = nullptr;
-        c->ws_bytes = 0;
-    }
-    size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-    hipError_t e = hipMalloc(&c->ws, want);
-    if (e != hipSuccess) return hip_fail(e);
-    c->ws_bytes = want;
-    return NHIP_OK;
-}
-
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Carve a list of sizes out of the workspace.
-template <size_t N>
-int carve(nhip_ctx* c, const size_t (&sizes)[N], void* (&ptrs)[N]) {
-    size_t total = 0;
-    for (size_t i = 0; i < N; ++i) total += align_up(sizes[i] ? sizes[i] : 1);
-    int rc = ensure_ws(c, total);
-    if (rc) return rc;
-    char* base = (char*)c->ws;
-    size_t off = 0;
-    for (size_t i = 0; i < N; ++i) {
-        ptrs[i] = base + off;
-        off += align_up(sizes[i] ? sizes[i] : 1);
-    }
-    return NHIP_OK;
-}
 
 // Batch verdict: any_bad |= (v[i] != 1) over n bytes; 16 B per lane per step, one atomic per wave.
 __global__ void __launch_bounds__(256) k_any_bad(const uint8_t* __restrict__ v, size_t n, uint32_t* __restrict__ any_bad) {
@@ -357,29 +271,23 @@ int nhip_mtree_verify_dev(nhip_ctx* c, const uint64_t* roots, size_t n_roots, co
 
 int nhip_verdicts_all_dev(nhip_ctx* c, const uint8_t* d_v, size_t n, uint8_t* all_ok) {
     if (!c || !all_ok || (n && !d_v)) return NHIP_ERR_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    const DeviceScope device_scope(c->device);
-    size_t sizes[1] = {sizeof(uint32_t)};
-    void* p[1];
-    int rc = carve(c, sizes, p);
-    if (rc) return rc;
-    uint32_t* d_out = (uint32_t*)p[0];
-    hipError_t e = hipMemsetAsync(d_out, 0, sizeof(uint32_t), c->stream);
-    if (e != hipSuccess) return hip_fail(e);
+    Stage st(c);
+    uint32_t* d_out;
+    st.tmp(d_out, 1);
+    if (st.commit()) return st.finish();
+    st.step([&] { return hip_fail(hipMemsetAsync(d_out, 0, sizeof(uint32_t), c->stream)); });
     size_t blocks = (n / 16 + 255) / 256;
     if (blocks < 1) blocks = 1;
     if (blocks > 1024) blocks = 1024;
-    rc = timed_launch(c, [&] {
+    st.launch([&] {
         hipLaunchKernelGGL(k_any_bad, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_v, n, d_out);
         return hipGetLastError();
     });
-    if (rc) return rc;
     uint32_t h = 1;
-    e = hipMemcpyAsync(&h, d_out, sizeof(h), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return hip_fail(e);
-    h = h ? 0u : 1u;
-    *all_ok = (uint8_t)(h ? 1 : 0);
+    st.out(&h, d_out, 1);
+    const int rc = st.finish();
+    if (rc) return rc;
+    *all_ok = (uint8_t)(h ? 0 : 1);
     return NHIP_OK;
 }
 
@@ -387,42 +295,28 @@ int nhip_verdicts_all_dev(nhip_ctx* c, const uint8_t* d_v, size_t n, uint8_t* al
 int nhip_tip5_permutation(nhip_ctx* c, uint64_t* states, size_t n) {
     if (!c || (n && !states)) return NHIP_ERR_ARG;
     if (n == 0) return NHIP_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    const DeviceScope device_scope(c->device);
-    const size_t bytes = n * 16 * sizeof(uint64_t);
-    size_t sizes[1] = {bytes};
-    void* p[1];
-    int rc = carve(c, sizes, p);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(p[0], states, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return hip_fail(e);
-    rc = timed_launch(c, [&] { return nhip::launch_permutation((uint64_t*)p[0], n, c->stream); });
-    if (rc) return rc;
-    e = hipMemcpyAsync(states, p[0], bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    return hip_fail(e);
+    Stage st(c);
+    uint64_t* d_states;
+    st.in(d_states, states, n, 16);
+    if (st.commit()) return st.finish();
+    st.launch([&] { return nhip::launch_permutation(d_states, n, c->stream); });
+    st.out(states, d_states, 16 * n);
+    return st.finish();
 }
 
 int nhip_tip5_hash_pair(nhip_ctx* c, const uint64_t* l, const uint64_t* r, size_t n, uint64_t* o) {
     if (!c || (n && (!l || !r || !o))) return NHIP_ERR_ARG;
     if (n == 0) return NHIP_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    const DeviceScope device_scope(c->device);
-    const size_t db = n * 5 * sizeof(uint64_t);
-    size_t sizes[3] = {db, db, db};
-    void* p[3];
-    int rc = carve(c, sizes, p);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(p[0], l, db, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p[1], r, db, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return hip_fail(e);
-    rc = timed_launch(c, [&] {
-        return nhip::launch_hash_pair((const uint64_t*)p[0], (const uint64_t*)p[1], (uint64_t*)p[2], n, c->stream);
-    });
-    if (rc) return rc;
-    e = hipMemcpyAsync(o, p[2], db, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    return hip_fail(e);
+    Stage st(c);
+    const uint64_t *d_l, *d_r;
+    uint64_t* d_o;
+    st.in(d_l, l, n, 5);
+    st.in(d_r, r, n, 5);
+    st.tmp(d_o, n, 5);
+    if (st.commit()) return st.finish();
+    st.launch([&] { return nhip::launch_hash_pair(d_l, d_r, d_o, n, c->stream); });
+    st.out(o, d_o, 5 * n);
+    return st.finish();
 }
 
 int nhip_tip5_hash_varlen(nhip_ctx* c, const uint64_t* data, const uint64_t* offsets, size_t n, uint64_t* o) {
@@ -432,41 +326,29 @@ int nhip_tip5_hash_varlen(nhip_ctx* c, const uint64_t* data, const uint64_t* off
         if (offsets[i + 1] < offsets[i]) return NHIP_ERR_ARG;
     const size_t total = (size_t)offsets[n];
     if (total && !data) return NHIP_ERR_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    const DeviceScope device_scope(c->device);
-    size_t sizes[3] = {total * sizeof(uint64_t), (n + 1) * sizeof(uint64_t), n * 5 * sizeof(uint64_t)};
-    void* p[3];
-    int rc = carve(c, sizes, p);
-    if (rc) return rc;
-    hipError_t e = hipSuccess;
-    if (total) e = hipMemcpyAsync(p[0], data, sizes[0], hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p[1], offsets, sizes[1], hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return hip_fail(e);
-    rc = timed_launch(c, [&] {
-        return nhip::launch_hash_varlen((const uint64_t*)p[0], (const uint64_t*)p[1], n, (uint64_t*)p[2], c->stream);
-    });
-    if (rc) return rc;
-    e = hipMemcpyAsync(o, p[2], sizes[2], hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    return hip_fail(e);
+    Stage st(c);
+    const uint64_t *d_data, *d_off;
+    uint64_t* d_o;
+    st.in(d_data, data, total);
+    st.in(d_off, offsets, n + 1);
+    st.tmp(d_o, n, 5);
+    if (st.commit()) return st.finish();
+    st.launch([&] { return nhip::launch_hash_varlen(d_data, d_off, n, d_o, c->stream); });
+    st.out(o, d_o, 5 * n);
+    return st.finish();
 }
 
 int nhip_mtree_build(nhip_ctx* c, const uint64_t* leafs, size_t n, uint64_t* nodes_out) {
     if (!c || !is_pow2(n) || !leafs || !nodes_out) return NHIP_ERR_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    const DeviceScope device_scope(c->device);
-    const size_t db = n * 5 * sizeof(uint64_t);
-    size_t sizes[2] = {db, db};
-    void* p[2];
-    int rc = carve(c, sizes, p);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(p[0], leafs, db, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return hip_fail(e);
-    rc = build_tree_dev(c, (const uint64_t*)p[0], n, (uint64_t*)p[1]);
-    if (rc) return rc;
-    e = hipMemcpyAsync(nodes_out, p[1], db, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    return hip_fail(e);
+    Stage st(c);
+    const uint64_t* d_leafs;
+    uint64_t* d_nodes;
+    st.in(d_leafs, leafs, n, 5);
+    st.tmp(d_nodes, n, 5);
+    if (st.commit()) return st.finish();
+    st.step([&] { return build_tree_dev(c, d_leafs, n, d_nodes); });
+    st.out(nodes_out, d_nodes, 5 * n);
+    return st.finish();
 }
 
 int nhip_mtree_verify(nhip_ctx* c, const uint64_t* roots, size_t n_roots, const uint64_t* idx,
@@ -474,28 +356,21 @@ int nhip_mtree_verify(nhip_ctx* c, const uint64_t* roots, size_t n_roots, const 
     if (!c || (n_roots != 1 && n_roots != n)) return NHIP_ERR_ARG;
     if (n == 0) return NHIP_OK;
     if (!roots || !idx || !leafs || !v || (depth && !paths)) return NHIP_ERR_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    const DeviceScope device_scope(c->device);
-    size_t sizes[5] = {n_roots * 5 * sizeof(uint64_t), n * sizeof(uint64_t), n * 5 * sizeof(uint64_t),
-                       n * (size_t)depth * 5 * sizeof(uint64_t), n};
-    void* p[5];
-    int rc = carve(c, sizes, p);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(p[0], roots, sizes[0], hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p[1], idx, sizes[1], hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p[2], leafs, sizes[2], hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && depth) e = hipMemcpyAsync(p[3], paths, sizes[3], hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return hip_fail(e);
+    Stage st(c);
+    const uint64_t *d_roots, *d_idx, *d_leafs, *d_paths;
+    uint8_t* d_v;
+    st.in(d_roots, roots, n_roots, 5);
+    st.in(d_idx, idx, n);
+    st.in(d_leafs, leafs, n, 5);
+    st.in(d_paths, paths, n, (size_t)depth * 5);
+    st.tmp(d_v, n);
+    if (st.commit()) return st.finish();
     const int per_path = (n_roots == n && n != 1) ? 1 : 0;
-    rc = timed_launch(c, [&] {
-        return nhip::launch_mtree_verify((const uint64_t*)p[0], per_path, (const uint64_t*)p[1],
-                                         (const uint64_t*)p[2], (const uint64_t*)p[3], depth, n, (uint8_t*)p[4],
-                                         c->stream);
+    st.launch([&] {
+        return nhip::launch_mtree_verify(d_roots, per_path, d_idx, d_leafs, d_paths, depth, n, d_v, c->stream);
     });
-    if (rc) return rc;
-    e = hipMemcpyAsync(v, p[4], n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    return hip_fail(e);
+    st.out(v, d_v, n);
+    return st.finish();
 }
 
 // ------------------------------------------------------------------ wire bytes -> words
@@ -520,12 +395,15 @@ int nhip_le_words_gpu(nhip_ctx* c, const uint8_t* bytes, size_t n_bytes, const n
         if (!out) return NHIP_ERR_ARG;
         nhip::WirePlan plan;
         nhip::wire_plan(bytes, spans, n, plan);
-        std::lock_guard<std::mutex> g(c->mu);
-        const DeviceScope device_scope(c->device);
-        size_t sizes[4] = {plan.raw_bytes, n * 8, n * sizeof(nhip::ProofIn), (size_t)total * 8};
-        void* p[4];
-        int rc = carve(c, sizes, p);
-        if (rc) return rc;
+        Stage st(c);
+        uint8_t* d_raw;
+        uint64_t *d_boff, *d_words;
+        nhip::ProofIn* d_in;
+        st.tmp(d_raw, plan.raw_bytes);
+        st.tmp(d_boff, n);
+        st.tmp(d_in, n);
+        st.tmp(d_words, (size_t)total);
+        if (st.commit()) return st.finish();
         bool any_pageable = false;
         for (const nhip::WireRun& r : plan.runs)
             any_pageable |= !nhip_internal_is_pinned(bytes + r.start, (size_t)(r.end - r.start));
@@ -538,23 +416,18 @@ int nhip_le_words_gpu(nhip_ctx* c, const uint8_t* bytes, size_t n_bytes, const n
                 stage = pageable.data();
             }
         }
-        hipError_t e = nhip::wire_upload(plan, bytes, (uint8_t*)p[0], stage,
-                                         [](const void* q, size_t b) { return nhip_internal_is_pinned(q, b) != 0; },
-                                         c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(p[1], plan.boff.data(), sizes[1], hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(p[2], in.data(), sizes[2], hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);  // the sources are this call's
-            return hip_fail(e);
-        }
-        rc = timed_launch(c, [&] {
-            return nhip::launch_wire_words((const uint8_t*)p[0], (const uint64_t*)p[1], (const nhip::ProofIn*)p[2],
-                                           (uint32_t)n, total, (uint64_t*)p[3], c->stream);
+        st.step([&] {
+            return hip_fail(nhip::wire_upload(plan, bytes, d_raw, stage,
+                                              [](const void* q, size_t b) { return nhip_internal_is_pinned(q, b) != 0; },
+                                              c->stream));
         });
-        if (rc == NHIP_OK) e = hipMemcpyAsync(out, p[3], sizes[3], hipMemcpyDeviceToHost, c->stream);
-        const hipError_t es = hipStreamSynchronize(c->stream);
-        if (rc) return rc;
-        return hip_fail(e != hipSuccess ? e : es);
+        st.up(d_boff, plan.boff.data(), n);  // after the raw runs, as the stream has always had them
+        st.up(d_in, in.data(), n);
+        st.launch([&] {
+            return nhip::launch_wire_words(d_raw, d_boff, d_in, (uint32_t)n, total, d_words, c->stream);
+        });
+        st.out(out, d_words, (size_t)total);
+        return st.finish();
     } catch (const std::bad_alloc&) {
         return NHIP_ERR_OOM;
     }
@@ -604,27 +477,18 @@ int nhip_mast_hash_batch(nhip_ctx* c, const uint64_t* data, const uint64_t* offs
     if (total && !data) return NHIP_ERR_ARG;
     uint32_t pow2 = 1;
     while (pow2 < fields) pow2 <<= 1;
-    std::lock_guard<std::mutex> g(c->mu);
-    const DeviceScope device_scope(c->device);
-    size_t sizes[4] = {total * 8, (nl + 1) * 8, nl * 40, n * 40};
-    void* p[4];
-    int rc = carve(c, sizes, p);
-    if (rc) return rc;
-    hipError_t e = hipSuccess;
-    if (total) e = hipMemcpyAsync(p[0], data, sizes[0], hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p[1], offsets, sizes[1], hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return hip_fail(e);
-    rc = timed_launch(c, [&] {
-        return nhip::launch_hash_varlen((const uint64_t*)p[0], (const uint64_t*)p[1], nl, (uint64_t*)p[2], c->stream);
-    });
-    if (rc) return rc;
-    rc = timed_launch(c, [&] {
-        return nhip::launch_mast_roots((const uint64_t*)p[2], fields, pow2, n, (uint64_t*)p[3], c->stream);
-    });
-    if (rc) return rc;
-    e = hipMemcpyAsync(roots_out, p[3], sizes[3], hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    return hip_fail(e);
+    Stage st(c);
+    const uint64_t *d_data, *d_off;
+    uint64_t *d_leaves, *d_roots;
+    st.in(d_data, data, total);
+    st.in(d_off, offsets, nl + 1);
+    st.tmp(d_leaves, nl, 5);
+    st.tmp(d_roots, n, 5);
+    if (st.commit()) return st.finish();
+    st.launch([&] { return nhip::launch_hash_varlen(d_data, d_off, nl, d_leaves, c->stream); });
+    st.launch([&] { return nhip::launch_mast_roots(d_leaves, fields, pow2, n, d_roots, c->stream); });
+    st.out(roots_out, d_roots, 5 * n);
+    return st.finish();
 }
 
 // AbsoluteIndexSet::compute (absolute_index_set.rs:86-113) for n removal records.
@@ -635,442 +499,21 @@ int nhip_absolute_index_sets(nhip_ctx* c, const uint64_t* items, const uint64_t*
                      !distances_out)))
         return NHIP_ERR_ARG;
     if (n == 0) return NHIP_OK;
-    std::vector<uint64_t> in(15 * n);
-    for (size_t i = 0; i < n; ++i)
-        for (int q = 0; q < 5; ++q) {
-            in[15 * i + q] = items[5 * i + q];
-            in[15 * i + 5 + q] = sender_randomness[5 * i + q];
-            in[15 * i + 10 + q] = receiver_preimages[5 * i + q];
-        }
-    std::lock_guard<std::mutex> g(c->mu);
-    const DeviceScope device_scope(c->device);
-    size_t sizes[4] = {15 * n * 8, n * 8, 2 * n * 8, 45 * n * 4};
-    void* p[4];
-    int rc = carve(c, sizes, p);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(p[0], in.data(), sizes[0], hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p[1], aocl_leaf_indices, sizes[1], hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) return hip_fail(e);
-    rc = timed_launch(c, [&] {
-        return nhip::launch_absolute_index_sets((const uint64_t*)p[0], (const uint64_t*)p[1], n, (uint64_t*)p[2],
-                                                (uint32_t*)p[3], c->stream);
-    });
-    if (rc) return rc;
-    e = hipMemcpyAsync(minimum_out, p[2], sizes[2], hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(distances_out, p[3], sizes[3], hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    return hip_fail(e);
-}
-
-// ------------------------------------------------------------------ mutator-set checks
-namespace {
-
-// Host-to-device copies of one call; the first HIP error sticks and later copies are skipped.
-struct Uploader {
-    hipStream_t st;
-    hipError_t e = hipSuccess;
-    void operator()(void* dst, const void* src, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
-    }
-};
-
-// Ends a staged call: the stream is drained on every path (the sources may be this call's own
-// temporaries), and a HIP error is never a verdict.
-int ms_finish(nhip_ctx* c, int rc, hipError_t e) {
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (rc) return rc;
-    return hip_fail(e != hipSuccess ? e : es);
-}
-
-}  // namespace
-
-// twenty-first MmrMembershipProof::verify for n (leaf, path) items against one MMR
-// (application/loops/peer_loop.rs:1235, protocol/peer.rs:824; path shape archival_mmr.rs:250-281).
-int nhip_mmr_verify_batch(nhip_ctx* c, const nhip_mmr* mmr, const uint64_t* leaf_index, const uint64_t* leaves,
-                          const uint64_t* path_off, const uint64_t* path, size_t n, uint8_t* verdicts) {
-    if (!c || nhip::ms_mmr_ok(mmr)) return NHIP_ERR_ARG;
-    if (n == 0) return NHIP_OK;
-    if (!leaf_index || !leaves || !verdicts || n > SIZE_MAX / 64) return NHIP_ERR_ARG;
-    uint64_t pd = 0;
-    if (nhip::ms_paths_ok(path_off, path, n, &pd)) return NHIP_ERR_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    const DeviceScope device_scope(c->device);
-    size_t sizes[6] = {(size_t)mmr->n_peaks * 40, n * 8, n * 40, (n + 1) * 8, (size_t)pd * 40, n};
-    void* p[6];
-    int rc = carve(c, sizes, p);
-    if (rc) return rc;
-    Uploader up{c->stream};
-    up(p[0], mmr->peaks, sizes[0]);
-    up(p[1], leaf_index, sizes[1]);
-    up(p[2], leaves, sizes[2]);
-    up(p[3], path_off, sizes[3]);
-    up(p[4], path, sizes[4]);
-    if (up.e != hipSuccess) return ms_finish(c, NHIP_OK, up.e);
-    const nhip::MmrDev dm{(const uint64_t*)p[0], mmr->n_peaks, mmr->num_leafs};
-    rc = timed_launch(c, [&] {
-        return nhip::launch_mmr_verify(dm, (const uint64_t*)p[1], (const uint64_t*)p[2], (const uint64_t*)p[3],
-                                       (const uint64_t*)p[4], n, (uint8_t*)p[5], c->stream);
-    });
-    hipError_t e = hipSuccess;
-    if (rc == NHIP_OK) e = hipMemcpyAsync(verdicts, p[5], n, hipMemcpyDeviceToHost, c->stream);
-    return ms_finish(c, rc, e);
-}
-
-// RemovalRecord::validate (removal_record.rs:202-251) and MutatorSetAccumulator::can_remove
-// (mutator_set_accumulator.rs:187-222) for n records (block/mod.rs:816-822, transaction_kernel.rs:129,145):
-// k_ms_chunk_auth over every dictionary entry, then k_ms_records.
-int nhip_ms_can_remove_batch(nhip_ctx* c, const nhip_msa* msa, const uint64_t* minimum, const uint32_t* distances,
-                             const nhip_ms_chunks* chunks, size_t n, uint8_t* valid, uint8_t* can_remove,
-                             uint8_t* status) {
-    if (!c || nhip::ms_msa_ok(msa)) return NHIP_ERR_ARG;
-    if (n == 0) return NHIP_OK;
-    if (!minimum || !distances || !valid || !can_remove || !status || n > SIZE_MAX / 256) return NHIP_ERR_ARG;
-    nhip::MsChunkCounts cc;
-    if (nhip::ms_chunks_ok(chunks, n, &cc)) return NHIP_ERR_ARG;
     try {
-        // membership is order-free: the kernel searches a sorted copy of the active window
-        std::vector<uint32_t> active(msa->active, msa->active + (msa->n_active ? msa->n_active : 0));
-        std::sort(active.begin(), active.end());
-        const size_t E = (size_t)cc.entries;
-        std::lock_guard<std::mutex> g(c->mu);
-        const DeviceScope device_scope(c->device);
-        size_t sizes[12] = {(size_t)msa->swbf_inactive.n_peaks * 40, active.size() * 4, n * 16, n * 45 * 4,
-                            (n + 1) * 8, E * 8, (E + 1) * 8, (size_t)cc.path_digests * 40, (E + 1) * 8,
-                            (size_t)cc.rel_words * 4, E, 3 * n};
-        void* p[12];
-        int rc = carve(c, sizes, p);
-        if (rc) return rc;
-        Uploader up{c->stream};
-        up(p[0], msa->swbf_inactive.peaks, sizes[0]);
-        up(p[1], active.data(), sizes[1]);
-        up(p[2], minimum, sizes[2]);
-        up(p[3], distances, sizes[3]);
-        up(p[4], chunks->entry_off, sizes[4]);
-        up(p[5], chunks->chunk_index, sizes[5]);
-        up(p[6], chunks->path_off, sizes[6]);
-        up(p[7], chunks->path, sizes[7]);
-        up(p[8], chunks->rel_off, sizes[8]);
-        up(p[9], chunks->rel, sizes[9]);
-        if (up.e != hipSuccess) return ms_finish(c, NHIP_OK, up.e);
-        const nhip::MmrDev swbf{(const uint64_t*)p[0], msa->swbf_inactive.n_peaks, msa->swbf_inactive.num_leafs};
-        rc = timed_launch(c, [&] {
-            return nhip::launch_ms_chunk_auth(swbf, (const uint64_t*)p[5], (const uint64_t*)p[6], (const uint64_t*)p[7],
-                                              (const uint64_t*)p[8], (const uint32_t*)p[9], E, (uint8_t*)p[10],
-                                              c->stream);
-        });
-        uint8_t* out = (uint8_t*)p[11];
-        if (rc == NHIP_OK) {
-            nhip::MsRecordsDev r{};
-            r.minimum = (const uint64_t*)p[2];
-            r.distances = (const uint32_t*)p[3];
-            r.entry_off = (const uint64_t*)p[4];
-            r.chunk_index = (const uint64_t*)p[5];
-            r.rel_off = (const uint64_t*)p[8];
-            r.rel = (const uint32_t*)p[9];
-            r.auth = (const uint8_t*)p[10];
-            r.aocl_member = nullptr;
-            r.active = (const uint32_t*)p[1];
-            r.n_active = active.size();
-            r.aocl_num_leafs = msa->aocl.num_leafs;
-            r.valid = out;
-            r.verdict = out + n;
-            r.status = out + 2 * n;
-            rc = timed_launch(c, [&] { return nhip::launch_ms_records(r, n, c->stream); });
-        }
-        hipError_t e = hipSuccess;
-        if (rc == NHIP_OK) e = hipMemcpyAsync(valid, out, n, hipMemcpyDeviceToHost, c->stream);
-        if (rc == NHIP_OK && e == hipSuccess) e = hipMemcpyAsync(can_remove, out + n, n, hipMemcpyDeviceToHost, c->stream);
-        if (rc == NHIP_OK && e == hipSuccess) e = hipMemcpyAsync(status, out + 2 * n, n, hipMemcpyDeviceToHost, c->stream);
-        return ms_finish(c, rc, e);
-    } catch (const std::bad_alloc&) {
-        return NHIP_ERR_OOM;
-    }
-}
-
-// MutatorSetAccumulator::verify (mutator_set_accumulator.rs:252-339) for n (item, membership proof) pairs
-// (wallet_state.rs:1796,1958; state/mod.rs:1050,1206,1341): k_ms_aocl_leaf, AbsoluteIndexSet::compute into
-// device buffers (no host round trip), k_ms_chunk_auth, k_ms_records.
-int nhip_ms_verify_batch(nhip_ctx* c, const nhip_msa* msa, const uint64_t* items, const uint64_t* sender_randomness,
-                         const uint64_t* receiver_preimages, const uint64_t* aocl_leaf_index,
-                         const uint64_t* aocl_path_off, const uint64_t* aocl_path, const nhip_ms_chunks* chunks,
-                         size_t n, uint8_t* verdicts, uint8_t* status) {
-    if (!c || nhip::ms_msa_ok(msa)) return NHIP_ERR_ARG;
-    if (n == 0) return NHIP_OK;
-    if (!items || !sender_randomness || !receiver_preimages || !aocl_leaf_index || !verdicts || !status ||
-        n > SIZE_MAX / 256)
-        return NHIP_ERR_ARG;
-    uint64_t apd = 0;
-    if (nhip::ms_paths_ok(aocl_path_off, aocl_path, n, &apd)) return NHIP_ERR_ARG;
-    nhip::MsChunkCounts cc;
-    if (nhip::ms_chunks_ok(chunks, n, &cc)) return NHIP_ERR_ARG;
-    try {
-        std::vector<uint32_t> active(msa->active, msa->active + (msa->n_active ? msa->n_active : 0));
-        std::sort(active.begin(), active.end());
-        std::vector<uint64_t> in(15 * n);
-        for (size_t i = 0; i < n; ++i)
-            for (int q = 0; q < 5; ++q) {
-                in[15 * i + q] = items[5 * i + q];
-                in[15 * i + 5 + q] = sender_randomness[5 * i + q];
-                in[15 * i + 10 + q] = receiver_preimages[5 * i + q];
-            }
-        const size_t E = (size_t)cc.entries;
-        std::lock_guard<std::mutex> g(c->mu);
-        const DeviceScope device_scope(c->device);
-        size_t sizes[18] = {(size_t)msa->aocl.n_peaks * 40, (size_t)msa->swbf_inactive.n_peaks * 40, active.size() * 4,
-                            15 * n * 8, n * 8, (n + 1) * 8, (size_t)apd * 40, (n + 1) * 8, E * 8, (E + 1) * 8,
-                            (size_t)cc.path_digests * 40, (E + 1) * 8, (size_t)cc.rel_words * 4,
-                            n * 16, n * 45 * 4, n, E, 2 * n};
-        void* p[18];
-        int rc = carve(c, sizes, p);
-        if (rc) return rc;
-        Uploader up{c->stream};
-        up(p[0], msa->aocl.peaks, sizes[0]);
-        up(p[1], msa->swbf_inactive.peaks, sizes[1]);
-        up(p[2], active.data(), sizes[2]);
-        up(p[3], in.data(), sizes[3]);
-        up(p[4], aocl_leaf_index, sizes[4]);
-        up(p[5], aocl_path_off, sizes[5]);
-        up(p[6], aocl_path, sizes[6]);
-        up(p[7], chunks->entry_off, sizes[7]);
-        up(p[8], chunks->chunk_index, sizes[8]);
-        up(p[9], chunks->path_off, sizes[9]);
-        up(p[10], chunks->path, sizes[10]);
-        up(p[11], chunks->rel_off, sizes[11]);
-        up(p[12], chunks->rel, sizes[12]);
-        if (up.e != hipSuccess) return ms_finish(c, NHIP_OK, up.e);
-        const nhip::MmrDev aocl{(const uint64_t*)p[0], msa->aocl.n_peaks, msa->aocl.num_leafs};
-        const nhip::MmrDev swbf{(const uint64_t*)p[1], msa->swbf_inactive.n_peaks, msa->swbf_inactive.num_leafs};
-        rc = timed_launch(c, [&] {
-            return nhip::launch_ms_aocl_leaf(aocl, (const uint64_t*)p[3], (const uint64_t*)p[4], (const uint64_t*)p[5],
-                                             (const uint64_t*)p[6], n, (uint8_t*)p[15], c->stream);
-        });
-        if (rc == NHIP_OK)
-            rc = timed_launch(c, [&] {
-                return nhip::launch_absolute_index_sets((const uint64_t*)p[3], (const uint64_t*)p[4], n,
-                                                        (uint64_t*)p[13], (uint32_t*)p[14], c->stream);
-            });
-        if (rc == NHIP_OK)
-            rc = timed_launch(c, [&] {
-                return nhip::launch_ms_chunk_auth(swbf, (const uint64_t*)p[8], (const uint64_t*)p[9],
-                                                  (const uint64_t*)p[10], (const uint64_t*)p[11],
-                                                  (const uint32_t*)p[12], E, (uint8_t*)p[16], c->stream);
-            });
-        uint8_t* out = (uint8_t*)p[17];
-        if (rc == NHIP_OK) {
-            nhip::MsRecordsDev r{};
-            r.minimum = (const uint64_t*)p[13];
-            r.distances = (const uint32_t*)p[14];
-            r.entry_off = (const uint64_t*)p[7];
-            r.chunk_index = (const uint64_t*)p[8];
-            r.rel_off = (const uint64_t*)p[11];
-            r.rel = (const uint32_t*)p[12];
-            r.auth = (const uint8_t*)p[16];
-            r.aocl_member = (const uint8_t*)p[15];
-            r.active = (const uint32_t*)p[2];
-            r.n_active = active.size();
-            r.aocl_num_leafs = msa->aocl.num_leafs;
-            r.valid = nullptr;
-            r.verdict = out;
-            r.status = out + n;
-            rc = timed_launch(c, [&] { return nhip::launch_ms_records(r, n, c->stream); });
-        }
-        hipError_t e = hipSuccess;
-        if (rc == NHIP_OK) e = hipMemcpyAsync(verdicts, out, n, hipMemcpyDeviceToHost, c->stream);
-        if (rc == NHIP_OK && e == hipSuccess) e = hipMemcpyAsync(status, out + n, n, hipMemcpyDeviceToHost, c->stream);
-        return ms_finish(c, rc, e);
-    } catch (const std::bad_alloc&) {
-        return NHIP_ERR_OOM;
-    }
-}
-
-// Block::validate rules 2.b-2.e and Block::mutator_set_accumulator_after for independent jobs (DESIGN.md
-// §6d): k_ms_chunk_auth_jobs, k_ms_records_jobs, k_ms_apply.  The host stages order only: sorted copies of
-// the active windows, each job's index slots sorted by (index, record) and grouped by chunk index, and its
-// records sorted by their index arrays.  It hashes nothing and decides nothing.
-int nhip_ms_apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out) {
-    using u128 = unsigned __int128;
-    nhip::MsApplyCounts cnt;
-    if (!c || nhip::ms_apply_ok(in, out, &cnt)) return NHIP_ERR_ARG;
-    const size_t n = in->n_jobs;
-    if (n == 0) return NHIP_OK;
-    try {
-        const size_t R = (size_t)cnt.records, E = (size_t)cnt.chunks.entries;
-        std::vector<nhip::MsApplyJob> jobs(n);
-        std::vector<uint64_t> peaks;
-        std::vector<uint32_t> active, exp_active, rec_job(R), entry_rec(E), idx_perm(45 * R), grp, rec_perm(R);
-        std::vector<u128> vals;
-        uint64_t dig_total = 0, grp_total = 0, win_total = 0;
-        auto put_peaks = [&](const nhip_mmr& m) {
-            const uint64_t off = peaks.size() / 5;
-            if (m.n_peaks) peaks.insert(peaks.end(), m.peaks, m.peaks + 5 * (size_t)m.n_peaks);
-            return off;
-        };
-        for (size_t j = 0; j < n; ++j) {
-            const nhip_msa& b = in->msa_before[j];
-            nhip::MsApplyJob& jb = jobs[j];
-            jb = nhip::MsApplyJob{};
-            jb.aocl_n = b.aocl.num_leafs;
-            jb.swbf_n = b.swbf_inactive.num_leafs;
-            jb.aocl_np = b.aocl.n_peaks;
-            jb.swbf_np = b.swbf_inactive.n_peaks;
-            jb.aocl_peaks = put_peaks(b.aocl);
-            jb.swbf_peaks = put_peaks(b.swbf_inactive);
-            jb.act_off = active.size();
-            jb.n_active = b.n_active;
-            if (b.n_active) active.insert(active.end(), b.active, b.active + b.n_active);
-            std::sort(active.begin() + jb.act_off, active.end());
-            jb.add_off = in->add_off[j];
-            jb.k = in->add_off[j + 1] - in->add_off[j];
-            jb.rec_off = in->rec_off[j];
-            jb.m = in->rec_off[j + 1] - in->rec_off[j];
-            if (in->msa_expected) {
-                const nhip_msa& x = in->msa_expected[j];
-                jb.exp_aocl_n = x.aocl.num_leafs;
-                jb.exp_swbf_n = x.swbf_inactive.num_leafs;
-                jb.exp_aocl_np = x.aocl.n_peaks;
-                jb.exp_swbf_np = x.swbf_inactive.n_peaks;
-                jb.exp_aocl_peaks = put_peaks(x.aocl);
-                jb.exp_swbf_peaks = put_peaks(x.swbf_inactive);
-                jb.exp_act_off = exp_active.size();
-                jb.exp_n_active = x.n_active;
-                if (x.n_active) exp_active.insert(exp_active.end(), x.active, x.active + x.n_active);
-            }
-            // order only: the job's index slots by (index, record), the runs of one chunk index, the records
-            // by their index arrays
-            const size_t m = (size_t)jb.m, r0 = (size_t)jb.rec_off;
-            vals.resize(45 * m);
-            for (size_t r = 0; r < m; ++r) {
-                rec_job[r0 + r] = (uint32_t)j;
-                const u128 mn = ((u128)in->minimum[2 * (r0 + r) + 1] << 64) | in->minimum[2 * (r0 + r)];
-                for (size_t t = 0; t < 45; ++t) vals[45 * r + t] = mn + in->distances[45 * (r0 + r) + t];
-                for (uint64_t e = in->chunks->entry_off[r0 + r]; e < in->chunks->entry_off[r0 + r + 1]; ++e)
-                    entry_rec[e] = (uint32_t)(r0 + r);
-            }
-            uint32_t* perm = idx_perm.data() + 45 * r0;
-            for (size_t s = 0; s < 45 * m; ++s) perm[s] = (uint32_t)s;
-            std::sort(perm, perm + 45 * m, [&](uint32_t x, uint32_t y) { return vals[x] != vals[y] ? vals[x] < vals[y] : x < y; });
-            jb.grp_off = grp_total;
-            for (size_t s = 0; s < 45 * m; ++s)
-                if (s == 0 || (vals[perm[s]] >> 12) != (vals[perm[s - 1]] >> 12)) {
-                    grp.push_back((uint32_t)s);
-                    ++jb.n_grp;
-                }
-            grp.push_back((uint32_t)(45 * m));
-            grp_total += jb.n_grp;
-            uint32_t* rp = rec_perm.data() + r0;
-            for (size_t r = 0; r < m; ++r) rp[r] = (uint32_t)r;
-            std::stable_sort(rp, rp + m, [&](uint32_t x, uint32_t y) {
-                return std::lexicographical_compare(vals.begin() + 45 * x, vals.begin() + 45 * x + 45,
-                                                    vals.begin() + 45 * y, vals.begin() + 45 * y + 45);
-            });
-            const uint64_t n1 = jb.aocl_n + jb.k;
-            const uint64_t slides =
-                n1 < jb.aocl_n ? 0 : (n1 ? n1 - 1 : 0) / 8 - (jb.aocl_n ? jb.aocl_n - 1 : 0) / 8;  // <= k / 8 + 1
-            jb.dig_off = dig_total;
-            dig_total += (jb.k + 1) + (2 * slides + 1) + 2 * jb.n_grp;
-            jb.win_off = cnt.accumulators ? out->active_off[j] : win_total;
-            jb.win_cap = cnt.accumulators ? out->active_off[j + 1] - out->active_off[j] : jb.n_active + 45 * jb.m;
-            win_total += jb.win_cap;
-        }
-        if (cnt.accumulators) win_total = cnt.window_cap;
-        const nhip_ms_chunks* ch = in->chunks;
-        std::lock_guard<std::mutex> g(c->mu);
-        const DeviceScope device_scope(c->device);
-        size_t sizes[29] = {n * sizeof(nhip::MsApplyJob), peaks.size() * 8, active.size() * 4, (size_t)cnt.additions * 40,
-                            R * 16, R * 45 * 4, R ? (R + 1) * 8 : 0, E * 8, R ? (E + 1) * 8 : 0,
-                            (size_t)cnt.chunks.path_digests * 40, R ? (E + 1) * 8 : 0, (size_t)cnt.chunks.rel_words * 4,
-                            R * 4, E * 4, R * 45 * 4, grp.size() * 4, R * 4, exp_active.size() * 4, E, 3 * R, 45 * R,
-                            (size_t)dig_total * 40, (size_t)grp_total * 16, 2 * n, n * 8, 2 * n * 64 * 40, 2 * n * 4,
-                            3 * n * 8, (size_t)win_total * 4};
-        void* p[29];
-        int rc = carve(c, sizes, p);
-        if (rc) return rc;
-        Uploader up{c->stream};
-        up(p[0], jobs.data(), sizes[0]);
-        up(p[1], peaks.data(), sizes[1]);
-        up(p[2], active.data(), sizes[2]);
-        up(p[3], in->additions, sizes[3]);
-        up(p[4], in->minimum, sizes[4]);
-        up(p[5], in->distances, sizes[5]);
-        if (R) {
-            up(p[6], ch->entry_off, sizes[6]);
-            up(p[7], ch->chunk_index, sizes[7]);
-            up(p[8], ch->path_off, sizes[8]);
-            up(p[9], ch->path, sizes[9]);
-            up(p[10], ch->rel_off, sizes[10]);
-            up(p[11], ch->rel, sizes[11]);
-        }
-        up(p[12], rec_job.data(), sizes[12]);
-        up(p[13], entry_rec.data(), sizes[13]);
-        up(p[14], idx_perm.data(), sizes[14]);
-        up(p[15], grp.data(), sizes[15]);
-        up(p[16], rec_perm.data(), sizes[16]);
-        up(p[17], exp_active.data(), sizes[17]);
-        if (up.e != hipSuccess) return ms_finish(c, NHIP_OK, up.e);
-        nhip::MsApplyDev a{};
-        a.jobs = (const nhip::MsApplyJob*)p[0];
-        a.peaks = (const uint64_t*)p[1];
-        a.active = (const uint32_t*)p[2];
-        a.additions = (const uint64_t*)p[3];
-        a.rec.minimum = (const uint64_t*)p[4];
-        a.rec.distances = (const uint32_t*)p[5];
-        a.rec.entry_off = (const uint64_t*)p[6];
-        a.rec.chunk_index = (const uint64_t*)p[7];
-        a.path_off = (const uint64_t*)p[8];
-        a.path = (const uint64_t*)p[9];
-        a.rec.rel_off = (const uint64_t*)p[10];
-        a.rec.rel = (const uint32_t*)p[11];
-        a.rec_job = (const uint32_t*)p[12];
-        a.entry_rec = (const uint32_t*)p[13];
-        a.idx_perm = (const uint32_t*)p[14];
-        a.grp = (const uint32_t*)p[15];
-        a.rec_perm = (const uint32_t*)p[16];
-        a.exp_active = (const uint32_t*)p[17];
-        a.has_expected = in->msa_expected ? 1 : 0;
-        a.rec.auth = (const uint8_t*)p[18];
-        a.rec.aocl_member = nullptr;
-        a.rec.valid = (uint8_t*)p[19];
-        a.rec.verdict = (uint8_t*)p[19] + R;
-        a.rec.status = (uint8_t*)p[19] + 2 * R;
-        a.index_set = (uint8_t*)p[20];
-        a.dig = (uint64_t*)p[21];
-        a.aux = (uint64_t*)p[22];
-        a.verdict = (uint8_t*)p[23];
-        a.status = (uint8_t*)p[23] + n;
-        a.bad = (uint64_t*)p[24];
-        a.out_peaks = (uint64_t*)p[25];
-        a.out_np = (uint32_t*)p[26];
-        a.out_n = (uint64_t*)p[27];
-        a.out_active = (uint32_t*)p[28];
-        rc = timed_launch(c, [&] { return nhip::launch_ms_chunk_auth_jobs(a, E, c->stream); });
-        if (rc == NHIP_OK) rc = timed_launch(c, [&] { return nhip::launch_ms_records_jobs(a, R, c->stream); });
-        if (rc == NHIP_OK) rc = timed_launch(c, [&] { return nhip::launch_ms_apply(a, n, c->stream); });
-        hipError_t e = hipSuccess;
-        auto down = [&](void* dst, const void* src, size_t bytes) {
-            if (rc == NHIP_OK && e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
-        };
-        // into temporaries first: the outputs stay untouched unless the whole call succeeds
-        std::vector<uint8_t> vs(2 * n);
-        std::vector<uint64_t> bad(n);
-        down(vs.data(), p[23], 2 * n);
-        down(bad.data(), p[24], n * 8);
-        if (cnt.accumulators) {
-            down(out->aocl_peaks, a.out_peaks, n * 64 * 40);
-            down(out->swbf_peaks, a.out_peaks + n * 64 * 5, n * 64 * 40);
-            down(out->aocl_n_peaks, a.out_np, n * 4);
-            down(out->swbf_n_peaks, a.out_np + n, n * 4);
-            down(out->aocl_num_leafs, a.out_n, n * 8);
-            down(out->swbf_num_leafs, a.out_n + n, n * 8);
-            down(out->n_active, a.out_n + 2 * n, n * 8);
-            down(out->active, a.out_active, (size_t)win_total * 4);
-        }
-        rc = ms_finish(c, rc, e);
-        if (rc == NHIP_OK) {
-            std::copy(vs.begin(), vs.begin() + n, out->verdict);
-            std::copy(vs.begin() + n, vs.end(), out->status);
-            std::copy(bad.begin(), bad.end(), out->bad_record);
-        }
-        return rc;
+        const std::vector<uint64_t> in = nhip::ms_interleave15(items, sender_randomness, receiver_preimages, n);
+        Stage st(c);
+        const uint64_t *d_in, *d_aocl;
+        uint64_t* d_min;
+        uint32_t* d_dist;
+        st.in(d_in, in.data(), n, 15);
+        st.in(d_aocl, aocl_leaf_indices, n);
+        st.tmp(d_min, n, 2);
+        st.tmp(d_dist, n, 45);
+        if (st.commit()) return st.finish();
+        st.launch([&] { return nhip::launch_absolute_index_sets(d_in, d_aocl, n, d_min, d_dist, c->stream); });
+        st.out(minimum_out, d_min, 2 * n);
+        st.out(distances_out, d_dist, 45 * n);
+        return st.finish();
     } catch (const std::bad_alloc&) {
         return NHIP_ERR_OOM;
     }

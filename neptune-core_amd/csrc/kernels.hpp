@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "ab_env.hpp"
+#include "ms_shape.hpp"
 #include "proof_codec.hpp"
 #include "stark.hpp"
 #include "xfe.hpp"
@@ -61,19 +62,7 @@ hipError_t launch_ms_chunk_auth(const MmrDev& swbf, const uint64_t* d_chunk_inde
 hipError_t launch_ms_records(const MsRecordsDev& r, size_t n, hipStream_t st);
 
 // ---- batched mutator-set updates (ms_apply_kernels.hip); every pointer a device pointer
-// One job as the host stages it: offsets into the pools of MsApplyDev (peaks and scratch in digests).
-struct MsApplyJob {
-    uint64_t aocl_n, swbf_n;          // msa_before: num_leafs
-    uint64_t aocl_peaks, swbf_peaks;  // ... and its peak lists in the peaks pool
-    uint64_t act_off, n_active;       // the sorted copy of its active window
-    uint64_t add_off, k;              // addition records
-    uint64_t rec_off, m;              // removal records (idx_perm: 45 rec_off; rec_perm: rec_off)
-    uint64_t grp_off, n_grp;          // groups before this job; its n_grp + 1 starts are grp[grp_off + job ..]
-    uint64_t dig_off;                 // digest scratch: k + 1, 2 slides + 1, 2 n_grp
-    uint64_t win_off, win_cap;        // the window after in out_active
-    uint64_t exp_aocl_n, exp_swbf_n, exp_aocl_peaks, exp_swbf_peaks, exp_act_off, exp_n_active;
-    uint32_t aocl_np, swbf_np, exp_aocl_np, exp_swbf_np;
-};
+// One job as the host stages it: MsApplyJob (ms_shape.hpp).
 struct MsApplyDev {
     const MsApplyJob* jobs;
     const uint64_t* peaks;       // canonical digests: every job's four peak lists

@@ -17,7 +17,7 @@
 //                              the two sorted lists it merges; the level-synchronous leaf mutation; SWBF
 //                              append; the window after; the comparison with the expected accumulator (2.e)
 //
-// The host stages order only (csrc/capi.hip): each job's active window sorted, its 45 m index slots
+// The host stages order only (csrc/ms_shape.cpp): each job's active window sorted, its 45 m index slots
 // sorted by (index, record) with the starts of the runs of one chunk index, and its records sorted by
 // their index arrays.  The device recomputes every index from minimum + distance and takes every
 // decision; a wrong order could only make it miss a duplicate or hash a wrong chunk.

@@ -1,0 +1,246 @@
+// C-ABI layer of libneptune_hip.so, the mutator-set entry points (declarations: include/neptune_hip.h;
+// DESIGN.md §6c, §6d).  Each is: validate shapes, stage order (both ms_shape.cpp), declare
+// the device buffers, commit, launch, read back (Stage in ctx.hpp).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "ctx.hpp"
+#include "kernels.hpp"
+#include "ms_shape.hpp"
+
+using nhip::Stage;
+
+namespace {
+
+// The flattened chunk dictionaries of n records (counts from ms_chunks_ok), in the order every call stages them
+void stage_chunks(Stage& st, const nhip_ms_chunks& ch, size_t n, const nhip::MsChunkCounts& cc, nhip::MsRecordsDev& r,
+                  const uint64_t*& path_off, const uint64_t*& path) {
+    const size_t E = (size_t)cc.entries;
+    st.in(r.entry_off, ch.entry_off, n ? n + 1 : 0);
+    st.in(r.chunk_index, ch.chunk_index, E);
+    st.in(path_off, ch.path_off, n ? E + 1 : 0);
+    st.in(path, ch.path, (size_t)cc.path_digests, 5);
+    st.in(r.rel_off, ch.rel_off, n ? E + 1 : 0);
+    st.in(r.rel, ch.rel, (size_t)cc.rel_words);
+}
+
+}  // namespace
+
+extern "C" {
+
+// twenty-first MmrMembershipProof::verify for n (leaf, path) items against one MMR
+// (application/loops/peer_loop.rs:1235, protocol/peer.rs:824; path shape archival_mmr.rs:250-281).
+int nhip_mmr_verify_batch(nhip_ctx* c, const nhip_mmr* mmr, const uint64_t* leaf_index, const uint64_t* leaves,
+                          const uint64_t* path_off, const uint64_t* path, size_t n, uint8_t* verdicts) {
+    if (!c || nhip::ms_mmr_ok(mmr)) return NHIP_ERR_ARG;
+    if (n == 0) return NHIP_OK;
+    if (!leaf_index || !leaves || !verdicts || n > SIZE_MAX / 64) return NHIP_ERR_ARG;
+    uint64_t pd = 0;
+    if (nhip::ms_paths_ok(path_off, path, n, &pd)) return NHIP_ERR_ARG;
+    Stage st(c);
+    nhip::MmrDev dm{nullptr, mmr->n_peaks, mmr->num_leafs};
+    const uint64_t *d_leaf_index, *d_leaves, *d_path_off, *d_path;
+    uint8_t* d_verdicts;
+    st.in(dm.peaks, mmr->peaks, mmr->n_peaks, 5);
+    st.in(d_leaf_index, leaf_index, n);
+    st.in(d_leaves, leaves, n, 5);
+    st.in(d_path_off, path_off, n + 1);
+    st.in(d_path, path, (size_t)pd, 5);
+    st.tmp(d_verdicts, n);
+    if (st.commit()) return st.finish();
+    st.launch([&] {
+        return nhip::launch_mmr_verify(dm, d_leaf_index, d_leaves, d_path_off, d_path, n, d_verdicts, c->stream);
+    });
+    st.out(verdicts, d_verdicts, n);
+    return st.finish();
+}
+
+// RemovalRecord::validate (removal_record.rs:202-251) and MutatorSetAccumulator::can_remove
+// (mutator_set_accumulator.rs:187-222) for n records (block/mod.rs:816-822, transaction_kernel.rs:129,145):
+// k_ms_chunk_auth over every dictionary entry, then k_ms_records.
+int nhip_ms_can_remove_batch(nhip_ctx* c, const nhip_msa* msa, const uint64_t* minimum, const uint32_t* distances,
+                             const nhip_ms_chunks* chunks, size_t n, uint8_t* valid, uint8_t* can_remove,
+                             uint8_t* status) {
+    if (!c || nhip::ms_msa_ok(msa)) return NHIP_ERR_ARG;
+    if (n == 0) return NHIP_OK;
+    if (!minimum || !distances || !valid || !can_remove || !status || n > SIZE_MAX / 256) return NHIP_ERR_ARG;
+    nhip::MsChunkCounts cc;
+    if (nhip::ms_chunks_ok(chunks, n, &cc)) return NHIP_ERR_ARG;
+    try {
+        std::vector<uint32_t> active;
+        nhip::ms_append_sorted_window(active, *msa);
+        const size_t E = (size_t)cc.entries;
+        Stage st(c);
+        nhip::MmrDev swbf{nullptr, msa->swbf_inactive.n_peaks, msa->swbf_inactive.num_leafs};
+        nhip::MsRecordsDev r{};  // aocl_member null: validate / can_remove
+        const uint64_t *d_path_off, *d_path;
+        uint8_t* d_auth;
+        st.in(swbf.peaks, msa->swbf_inactive.peaks, msa->swbf_inactive.n_peaks, 5);
+        st.in(r.active, active.data(), active.size());
+        st.in(r.minimum, minimum, n, 2);
+        st.in(r.distances, distances, n, 45);
+        stage_chunks(st, *chunks, n, cc, r, d_path_off, d_path);
+        st.tmp(d_auth, E);
+        st.tmp(r.valid, n, 3);  // valid, verdict, status
+        if (st.commit()) return st.finish();
+        r.auth = d_auth;
+        r.n_active = active.size();
+        r.aocl_num_leafs = msa->aocl.num_leafs;
+        r.verdict = r.valid + n;
+        r.status = r.valid + 2 * n;
+        st.launch([&] {
+            return nhip::launch_ms_chunk_auth(swbf, r.chunk_index, d_path_off, d_path, r.rel_off, r.rel, E, d_auth, c->stream);
+        });
+        st.launch([&] { return nhip::launch_ms_records(r, n, c->stream); });
+        st.out(valid, r.valid, n);
+        st.out(can_remove, r.verdict, n);
+        st.out(status, r.status, n);
+        return st.finish();
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// MutatorSetAccumulator::verify (mutator_set_accumulator.rs:252-339) for n (item, membership proof) pairs
+// (wallet_state.rs:1796,1958; state/mod.rs:1050,1206,1341): k_ms_aocl_leaf, AbsoluteIndexSet::compute into
+// device buffers (no host round trip), k_ms_chunk_auth, k_ms_records.
+int nhip_ms_verify_batch(nhip_ctx* c, const nhip_msa* msa, const uint64_t* items, const uint64_t* sender_randomness,
+                         const uint64_t* receiver_preimages, const uint64_t* aocl_leaf_index,
+                         const uint64_t* aocl_path_off, const uint64_t* aocl_path, const nhip_ms_chunks* chunks,
+                         size_t n, uint8_t* verdicts, uint8_t* status) {
+    if (!c || nhip::ms_msa_ok(msa)) return NHIP_ERR_ARG;
+    if (n == 0) return NHIP_OK;
+    if (!items || !sender_randomness || !receiver_preimages || !aocl_leaf_index || !verdicts || !status ||
+        n > SIZE_MAX / 256)
+        return NHIP_ERR_ARG;
+    uint64_t apd = 0;
+    if (nhip::ms_paths_ok(aocl_path_off, aocl_path, n, &apd)) return NHIP_ERR_ARG;
+    nhip::MsChunkCounts cc;
+    if (nhip::ms_chunks_ok(chunks, n, &cc)) return NHIP_ERR_ARG;
+    try {
+        std::vector<uint32_t> active;
+        nhip::ms_append_sorted_window(active, *msa);
+        const std::vector<uint64_t> in = nhip::ms_interleave15(items, sender_randomness, receiver_preimages, n);
+        const size_t E = (size_t)cc.entries;
+        Stage st(c);
+        nhip::MmrDev aocl{nullptr, msa->aocl.n_peaks, msa->aocl.num_leafs};
+        nhip::MmrDev swbf{nullptr, msa->swbf_inactive.n_peaks, msa->swbf_inactive.num_leafs};
+        nhip::MsRecordsDev r{};  // valid null: verify
+        const uint64_t *d_in, *d_leaf_index, *d_aocl_path_off, *d_aocl_path, *d_path_off, *d_path;
+        uint64_t* d_minimum;
+        uint32_t* d_distances;
+        uint8_t *d_member, *d_auth;
+        st.in(aocl.peaks, msa->aocl.peaks, msa->aocl.n_peaks, 5);
+        st.in(swbf.peaks, msa->swbf_inactive.peaks, msa->swbf_inactive.n_peaks, 5);
+        st.in(r.active, active.data(), active.size());
+        st.in(d_in, in.data(), n, 15);
+        st.in(d_leaf_index, aocl_leaf_index, n);
+        st.in(d_aocl_path_off, aocl_path_off, n + 1);
+        st.in(d_aocl_path, aocl_path, (size_t)apd, 5);
+        stage_chunks(st, *chunks, n, cc, r, d_path_off, d_path);
+        st.tmp(d_minimum, n, 2);
+        st.tmp(d_distances, n, 45);
+        st.tmp(d_member, n);
+        st.tmp(d_auth, E);
+        st.tmp(r.verdict, n, 2);  // verdict, status
+        if (st.commit()) return st.finish();
+        r.minimum = d_minimum;
+        r.distances = d_distances;
+        r.aocl_member = d_member;
+        r.auth = d_auth;
+        r.n_active = active.size();
+        r.aocl_num_leafs = msa->aocl.num_leafs;
+        r.status = r.verdict + n;
+        st.launch([&] {
+            return nhip::launch_ms_aocl_leaf(aocl, d_in, d_leaf_index, d_aocl_path_off, d_aocl_path, n, d_member, c->stream);
+        });
+        st.launch([&] { return nhip::launch_absolute_index_sets(d_in, d_leaf_index, n, d_minimum, d_distances, c->stream); });
+        st.launch([&] {
+            return nhip::launch_ms_chunk_auth(swbf, r.chunk_index, d_path_off, d_path, r.rel_off, r.rel, E, d_auth, c->stream);
+        });
+        st.launch([&] { return nhip::launch_ms_records(r, n, c->stream); });
+        st.out(verdicts, r.verdict, n);
+        st.out(status, r.status, n);
+        return st.finish();
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// Block::validate rules 2.b-2.e and Block::mutator_set_accumulator_after for independent jobs (DESIGN.md
+// §6d): k_ms_chunk_auth_jobs, k_ms_records_jobs, k_ms_apply.  The host stages order only (ms_shape.cpp).
+int nhip_ms_apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out) {
+    nhip::MsApplyCounts cnt;
+    if (!c || nhip::ms_apply_ok(in, out, &cnt)) return NHIP_ERR_ARG;
+    const size_t n = in->n_jobs;
+    if (n == 0) return NHIP_OK;
+    try {
+        const size_t R = (size_t)cnt.records, E = (size_t)cnt.chunks.entries;
+        nhip::MsApplyOrder o;
+        nhip::ms_apply_order(in, out, cnt, &o);
+        const nhip_ms_chunks none{};  // no record: the dictionaries may be absent
+        Stage st(c);
+        nhip::MsApplyDev a{};  // rec.aocl_member null: the records as can_remove decides them
+        a.has_expected = in->msa_expected ? 1 : 0;
+        st.in(a.jobs, o.jobs.data(), n);
+        st.in(a.peaks, o.peaks.data(), o.peaks.size());
+        st.in(a.active, o.active.data(), o.active.size());
+        st.in(a.additions, in->additions, (size_t)cnt.additions, 5);
+        st.in(a.rec.minimum, in->minimum, R, 2);
+        st.in(a.rec.distances, in->distances, R, 45);
+        stage_chunks(st, R ? *in->chunks : none, R, cnt.chunks, a.rec, a.path_off, a.path);
+        st.in(a.rec_job, o.rec_job.data(), R);
+        st.in(a.entry_rec, o.entry_rec.data(), E);
+        st.in(a.idx_perm, o.idx_perm.data(), R, 45);
+        st.in(a.grp, o.grp.data(), o.grp.size());
+        st.in(a.rec_perm, o.rec_perm.data(), R);
+        st.in(a.exp_active, o.exp_active.data(), o.exp_active.size());
+        st.tmp(a.rec.auth, E);
+        st.tmp(a.rec.valid, R, 3);  // per record: valid, verdict, status
+        st.tmp(a.index_set, R, 45);
+        st.tmp(a.dig, (size_t)o.dig_total, 5);
+        st.tmp(a.aux, (size_t)o.grp_total, 2);
+        st.tmp(a.verdict, n, 2);  // per job: verdict, status
+        st.tmp(a.bad, n);
+        st.tmp(a.out_peaks, 2 * n, 64 * 5);  // AOCL, SWBF
+        st.tmp(a.out_np, n, 2);
+        st.tmp(a.out_n, n, 3);  // aocl.num_leafs, swbf_inactive.num_leafs, n_active
+        st.tmp(a.out_active, (size_t)o.win_total);
+        if (st.commit()) return st.finish();
+        a.rec.verdict = a.rec.valid + R;
+        a.rec.status = a.rec.valid + 2 * R;
+        a.status = a.verdict + n;
+        st.launch([&] { return nhip::launch_ms_chunk_auth_jobs(a, E, c->stream); });
+        st.launch([&] { return nhip::launch_ms_records_jobs(a, R, c->stream); });
+        st.launch([&] { return nhip::launch_ms_apply(a, n, c->stream); });
+        // into temporaries first: the outputs stay untouched unless the whole call succeeds
+        std::vector<uint8_t> vs(2 * n);
+        std::vector<uint64_t> bad(n);
+        st.out(vs.data(), a.verdict, 2 * n);
+        st.out(bad.data(), a.bad, n);
+        if (cnt.accumulators) {
+            st.out(out->aocl_peaks, a.out_peaks, n * 64 * 5);
+            st.out(out->swbf_peaks, a.out_peaks, n * 64 * 5, n * 64 * 5);
+            st.out(out->aocl_n_peaks, a.out_np, n);
+            st.out(out->swbf_n_peaks, a.out_np, n, n);
+            st.out(out->aocl_num_leafs, a.out_n, n);
+            st.out(out->swbf_num_leafs, a.out_n, n, n);
+            st.out(out->n_active, a.out_n, n, 2 * n);
+            st.out(out->active, a.out_active, (size_t)o.win_total);
+        }
+        const int rc = st.finish();
+        if (rc == NHIP_OK) {
+            std::copy(vs.begin(), vs.begin() + n, out->verdict);
+            std::copy(vs.begin() + n, vs.end(), out->status);
+            std::copy(bad.begin(), bad.end(), out->bad_record);
+        }
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
-// Shape checks of the mutator-set entry points (nhip_mmr_verify_batch, nhip_ms_can_remove_batch,
-// nhip_ms_verify_batch, nhip_ms_apply_batch): the only thing the host decides about their inputs.  Every verdict is the
+// Host side of the mutator-set entry points (nhip_mmr_verify_batch, nhip_ms_can_remove_batch,
+// nhip_ms_verify_batch, nhip_ms_apply_batch): shape checks, the only thing the host decides about their inputs,
+// and the order it stages besides the caller's own arrays.  Every verdict is the
 // device's; the host refuses (NHIP_ERR_ARG) what it could not stage without reading outside the
 // caller's arrays: a null pointer with a non-zero count, an offset array that does not start at 0
 // or decreases, and totals whose byte size leaves size_t.  Host only (no HIP), so that
@@ -7,6 +8,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#include <vector>
 
 #include "../../include/neptune_hip.h"
 
@@ -40,5 +43,42 @@ struct MsApplyCounts {
 // ms_chunks_ok, at most (2^32 - 1) / 45 records in a job, the accumulator outputs all null or all present,
 // and every job's window capacity >= n_active + 45 records.  Hashes nothing, decides nothing.
 int ms_apply_ok(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, MsApplyCounts* counts);
+
+// ---- staged order: inputs that passed the checks above; hashes nothing, decides nothing;
+// may throw std::bad_alloc
+
+// Appends the accumulator's active window to pool and sorts what it appended (membership is order-free: the
+// kernels search a sorted copy).
+void ms_append_sorted_window(std::vector<uint32_t>& pool, const nhip_msa& msa);
+
+// The 15 words (item, sender_randomness, receiver_preimage) of each of n records, record by record.
+std::vector<uint64_t> ms_interleave15(const uint64_t* items, const uint64_t* sender_randomness,
+                                      const uint64_t* receiver_preimages, size_t n);
+
+// One job of nhip_ms_apply_batch as the host stages it and k_ms_apply reads it (ms_apply_kernels.hip): offsets
+// into the pools of MsApplyDev (kernels.hpp; peaks and scratch in digests).
+struct MsApplyJob {
+    uint64_t aocl_n, swbf_n;          // msa_before: num_leafs
+    uint64_t aocl_peaks, swbf_peaks;  // ... and its peak lists in the peaks pool
+    uint64_t act_off, n_active;       // the sorted copy of its active window
+    uint64_t add_off, k;              // addition records
+    uint64_t rec_off, m;              // removal records (idx_perm: 45 rec_off; rec_perm: rec_off)
+    uint64_t grp_off, n_grp;          // groups before this job; its n_grp + 1 starts are grp[grp_off + job ..]
+    uint64_t dig_off;                 // digest scratch: k + 1, 2 slides + 1, 2 n_grp
+    uint64_t win_off, win_cap;        // the window after in out_active
+    uint64_t exp_aocl_n, exp_swbf_n, exp_aocl_peaks, exp_swbf_peaks, exp_act_off, exp_n_active;
+    uint32_t aocl_np, swbf_np, exp_aocl_np, exp_swbf_np;
+};
+// nhip_ms_apply_batch's staged arrays (MsApplyDev says what the kernels read in each): per job a sorted copy of
+// its window, its index slots sorted by (index, slot) and grouped by chunk index, its records sorted by their
+// index arrays (stable), and its offsets into every pool.
+struct MsApplyOrder {
+    std::vector<MsApplyJob> jobs;
+    std::vector<uint64_t> peaks;
+    std::vector<uint32_t> active, exp_active, rec_job, entry_rec, idx_perm, grp, rec_perm;
+    uint64_t dig_total = 0, grp_total = 0, win_total = 0;
+};
+void ms_apply_order(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, const MsApplyCounts& cnt,
+                    MsApplyOrder* o);
 
 }  // namespace nhip

@@ -1,4 +1,4 @@
-# Host-only sanitizer build of nhip_ms_apply_batch's shape validator (tests/test_ms_apply_ref.py):
+# Host-only sanitizer build of nhip_ms_apply_batch's shape validator and staged order (tests/test_ms_apply_ref.py):
 # make -f ms_apply_shape.mk -C tests/native OUT=<dir>.  csrc/ms_shape.cpp is a host-only translation unit, so
 # the stand-alone check links without HIP; same sanitizer flags as ms_shape.mk beside it.
 CSRC := ../../neptune-core_amd/csrc

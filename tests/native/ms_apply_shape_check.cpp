@@ -1,8 +1,11 @@
-// Host-side shape validator of nhip_ms_apply_batch (csrc/ms_shape.cpp: ms_apply_ok) under ASan + UBSan
-// (tests/test_ms_apply_ref.py): good and malformed job batches, every array an exactly sized heap block so
-// that a read past the declared shapes is a sanitizer report.  Host only: links no HIP.
+// Host side of nhip_ms_apply_batch under ASan + UBSan (tests/test_ms_apply_ref.py): the shape validator
+// (csrc/ms_shape.cpp: ms_apply_ok) on good and malformed job batches, and the staged order (ms_apply_order
+// beside it) on the fixed batch and on seeded random ones against a naive recomputation.  Every array is
+// an exactly sized heap block, so that a read past the declared shapes is a sanitizer report.  Host only:
+// links no HIP.
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "../../neptune-core_amd/csrc/ms_shape.hpp"
@@ -83,6 +86,281 @@ int check(Batch& b, nhip::MsApplyCounts* c = nullptr) {
     const nhip_ms_apply_out out = b.out();
     return nhip::ms_apply_ok(&in, &out, c);
 }
+
+// ---------------------------------------------------------------- the staged order
+using u128 = unsigned __int128;
+
+void fail(const std::string& what, const char* why, size_t j) {
+    std::fprintf(stderr, "FAIL order %s: %s (job %zu)\n", what.c_str(), why, j);
+    ++failures;
+}
+#define CHECK(cond, why) \
+    do {                 \
+        if (!(cond)) {   \
+            fail(what, why, j); \
+            return;      \
+        }                \
+    } while (0)
+
+bool lex_less(const u128* a, const u128* b) {
+    for (int t = 0; t < 45; ++t)
+        if (a[t] != b[t]) return a[t] < b[t];
+    return false;
+}
+std::vector<uint32_t> insertion_sorted(const uint32_t* p, size_t n) {
+    std::vector<uint32_t> v(p, p + n);
+    for (size_t i = 1; i < v.size(); ++i)
+        for (size_t q = i; q > 0 && v[q] < v[q - 1]; --q) std::swap(v[q], v[q - 1]);
+    return v;
+}
+bool peaks_at(const nhip::MsApplyOrder& o, uint64_t off, const nhip_mmr& m) {
+    if (5 * (off + m.n_peaks) > o.peaks.size()) return false;
+    for (size_t q = 0; q < 5 * (size_t)m.n_peaks; ++q)
+        if (o.peaks[5 * off + q] != m.peaks[q]) return false;
+    return true;
+}
+
+// ms_apply_order's output for a batch that ms_apply_ok accepts, field by field against what the comments of
+// MsApplyJob / MsApplyDev (csrc/ms_shape.hpp, kernels.hpp) promise the kernels
+void check_order(const nhip_ms_apply_in& in, const nhip_ms_apply_out& out, const std::string& what) {
+    nhip::MsApplyCounts cnt;
+    size_t j = 0;
+    CHECK(nhip::ms_apply_ok(&in, &out, &cnt) == NHIP_OK, "the batch is refused");
+    nhip::MsApplyOrder o;
+    nhip::ms_apply_order(&in, &out, cnt, &o);
+    const size_t n = in.n_jobs, R = (size_t)cnt.records, E = (size_t)cnt.chunks.entries;
+    CHECK(o.jobs.size() == n && o.rec_job.size() == R && o.entry_rec.size() == E && o.idx_perm.size() == 45 * R &&
+              o.rec_perm.size() == R,
+          "array sizes");
+    uint64_t peaks = 0, act = 0, exp_act = 0, grp = 0, dig = 0, win = 0;
+    for (j = 0; j < n; ++j) {
+        const nhip_msa& b = in.msa_before[j];
+        const nhip::MsApplyJob& jb = o.jobs[j];
+        const size_t r0 = (size_t)in.rec_off[j], m = (size_t)(in.rec_off[j + 1] - in.rec_off[j]);
+        CHECK(jb.aocl_n == b.aocl.num_leafs && jb.swbf_n == b.swbf_inactive.num_leafs && jb.aocl_np == b.aocl.n_peaks &&
+                  jb.swbf_np == b.swbf_inactive.n_peaks && jb.n_active == b.n_active && jb.add_off == in.add_off[j] &&
+                  jb.k == in.add_off[j + 1] - in.add_off[j] && jb.rec_off == r0 && jb.m == m,
+              "the job's counts");
+        // the peak offsets address the right five-word digests
+        CHECK(jb.aocl_peaks == peaks && peaks_at(o, jb.aocl_peaks, b.aocl), "aocl peaks");
+        peaks += b.aocl.n_peaks;
+        CHECK(jb.swbf_peaks == peaks && peaks_at(o, jb.swbf_peaks, b.swbf_inactive), "swbf peaks");
+        peaks += b.swbf_inactive.n_peaks;
+        // the window: sorted, a permutation of the input
+        CHECK(jb.act_off == act && act + b.n_active <= o.active.size(), "act_off");
+        const std::vector<uint32_t> sorted = insertion_sorted(b.active, (size_t)b.n_active);
+        for (size_t q = 0; q < sorted.size(); ++q) CHECK(o.active[act + q] == sorted[q], "the sorted window");
+        act += b.n_active;
+        if (in.msa_expected) {
+            const nhip_msa& x = in.msa_expected[j];
+            CHECK(jb.exp_aocl_n == x.aocl.num_leafs && jb.exp_swbf_n == x.swbf_inactive.num_leafs &&
+                      jb.exp_aocl_np == x.aocl.n_peaks && jb.exp_swbf_np == x.swbf_inactive.n_peaks &&
+                      jb.exp_n_active == x.n_active,
+                  "the expected counts");
+            CHECK(jb.exp_aocl_peaks == peaks && peaks_at(o, jb.exp_aocl_peaks, x.aocl), "expected aocl peaks");
+            peaks += x.aocl.n_peaks;
+            CHECK(jb.exp_swbf_peaks == peaks && peaks_at(o, jb.exp_swbf_peaks, x.swbf_inactive), "expected swbf peaks");
+            peaks += x.swbf_inactive.n_peaks;
+            // the expected window keeps the caller's order
+            CHECK(jb.exp_act_off == exp_act && exp_act + x.n_active <= o.exp_active.size(), "exp_act_off");
+            for (size_t q = 0; q < x.n_active; ++q) CHECK(o.exp_active[exp_act + q] == x.active[q], "the expected window");
+            exp_act += x.n_active;
+        } else {
+            CHECK(!jb.exp_aocl_n && !jb.exp_swbf_n && !jb.exp_aocl_np && !jb.exp_swbf_np && !jb.exp_n_active &&
+                      !jb.exp_aocl_peaks && !jb.exp_swbf_peaks && !jb.exp_act_off,
+                  "expected fields without an expected accumulator");
+        }
+        // the indices, recomputed
+        std::vector<u128> val(45 * m);
+        for (size_t r = 0; r < m; ++r) {
+            CHECK(o.rec_job[r0 + r] == j, "rec_job");
+            for (uint64_t e = in.chunks->entry_off[r0 + r]; e < in.chunks->entry_off[r0 + r + 1]; ++e)
+                CHECK(o.entry_rec[e] == r0 + r, "entry_rec");
+            u128 mn = in.minimum[2 * (r0 + r) + 1];
+            mn = (mn << 64) + in.minimum[2 * (r0 + r)];
+            for (size_t t = 0; t < 45; ++t) val[45 * r + t] = mn + in.distances[45 * (r0 + r) + t];
+        }
+        // idx_perm: a permutation of 0 .. 45 m ordered by (index, slot)
+        const uint32_t* perm = o.idx_perm.data() + 45 * r0;
+        std::vector<uint8_t> seen(45 * m, 0);
+        for (size_t s = 0; s < 45 * m; ++s) {
+            CHECK(perm[s] < 45 * m && !seen[perm[s]], "idx_perm is no permutation");
+            seen[perm[s]] = 1;
+            if (s)
+                CHECK(val[perm[s - 1]] < val[perm[s]] || (val[perm[s - 1]] == val[perm[s]] && perm[s - 1] < perm[s]),
+                      "idx_perm is not ordered by (index, slot)");
+        }
+        // grp: the positions where index >> 12 changes, then 45 m; n_grp and grp_off the running counts
+        std::vector<uint32_t> starts;
+        for (size_t s = 0; s < 45 * m; ++s)
+            if (s == 0 || (val[perm[s]] >> 12) != (val[perm[s - 1]] >> 12)) starts.push_back((uint32_t)s);
+        CHECK(jb.n_grp == starts.size() && jb.grp_off == grp, "n_grp / grp_off");
+        starts.push_back((uint32_t)(45 * m));
+        CHECK(grp + j + starts.size() <= o.grp.size(), "grp is short");
+        for (size_t q = 0; q < starts.size(); ++q) CHECK(o.grp[grp + j + q] == starts[q], "grp");
+        grp += jb.n_grp;
+        // rec_perm: the stable lexicographic order of the 45-element arrays
+        std::vector<uint32_t> want(m);
+        for (size_t r = 0; r < m; ++r) {
+            size_t q = r;
+            for (; q > 0 && lex_less(&val[45 * r], &val[45 * want[q - 1]]); --q) want[q] = want[q - 1];
+            want[q] = (uint32_t)r;
+        }
+        for (size_t r = 0; r < m; ++r) CHECK(o.rec_perm[r0 + r] == want[r], "rec_perm");
+        // the digest scratch
+        const uint64_t n0 = b.aocl.num_leafs, n1 = n0 + jb.k;
+        const uint64_t slides = n1 < n0 ? 0 : (n1 ? n1 - 1 : 0) / 8 - (n0 ? n0 - 1 : 0) / 8;
+        CHECK(jb.dig_off == dig, "dig_off");
+        dig += (jb.k + 1) + (2 * slides + 1) + 2 * jb.n_grp;
+        // the window after
+        if (cnt.accumulators) {
+            CHECK(jb.win_off == out.active_off[j] && jb.win_cap == out.active_off[j + 1] - out.active_off[j],
+                  "win_off / win_cap from active_off");
+        } else {
+            CHECK(jb.win_off == win && jb.win_cap == b.n_active + 45 * m, "win_off / win_cap");
+        }
+        win += jb.win_cap;
+    }
+    j = n;
+    CHECK(o.peaks.size() == 5 * peaks && o.active.size() == act && o.exp_active.size() == exp_act, "pool sizes");
+    CHECK(o.grp.size() == grp + n && o.grp_total == grp && o.dig_total == dig, "grp / dig totals");
+    CHECK(o.win_total == (cnt.accumulators ? cnt.window_cap : win), "win_total");
+    ++good;
+}
+
+struct Rng {  // splitmix64
+    uint64_t s;
+    uint64_t next() {
+        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    }
+    uint64_t below(uint64_t n) { return next() % n; }
+};
+
+enum Special { PLAIN, HIGH_WORD, CROSS_2_64 };
+
+// 1 to 5 jobs, 0 to 6 records and 0 to 9 additions per job, windows of 0 to 12 unsorted indices; minima a few
+// indices below a multiple of 2,048 (every other one a chunk boundary) and distances below 16, a few of them one
+// chunk further, so that records share indices and straddle a multiple of 4,096 or stay inside a chunk; a third
+// of the records repeat an earlier record of their job
+struct RandomBatch {
+    std::vector<std::vector<uint64_t>> peak_lists;  // four per job
+    std::vector<std::vector<uint32_t>> windows;     // two per job
+    std::vector<nhip_msa> before, expected;
+    std::vector<uint64_t> add_off, additions, rec_off, minimum;
+    std::vector<uint32_t> distances;
+    std::vector<uint64_t> entry_off, chunk_index, path_off, path, rel_off;
+    std::vector<uint32_t> rel;
+    nhip_ms_chunks chunks;
+    std::vector<uint8_t> verdict, status;
+    std::vector<uint64_t> bad_record, o_aocl, o_swbf, o_an, o_sn, o_nact, active_off;
+    std::vector<uint32_t> o_anp, o_snp, o_active;
+    bool with_expected, with_acc;
+
+    RandomBatch(uint64_t seed, Special special) {
+        Rng g{seed};
+        const size_t n = 1 + g.below(5);
+        with_expected = g.below(2);
+        with_acc = g.below(2);
+        const uint64_t half_chunk = 1 + g.below(6);
+        add_off = rec_off = active_off = {0};
+        entry_off = path_off = rel_off = {0};
+        auto mmr = [&]() {
+            const uint32_t np = (uint32_t)g.below(4);
+            std::vector<uint64_t> p(5 * np);  // exactly sized
+            for (uint64_t& w : p) w = g.next();
+            peak_lists.push_back(p);
+            const uint64_t leafs = g.below(4) ? g.below(40) : g.next();
+            return nhip_mmr{ptr(peak_lists.back()), np, leafs};
+        };
+        auto msa = [&]() {
+            const nhip_mmr a = mmr(), s = mmr();
+            std::vector<uint32_t> w(g.below(13));
+            for (uint32_t& x : w) x = (uint32_t)g.below(20);
+            windows.push_back(w);
+            return nhip_msa{a, s, ptr(windows.back()), windows.back().size()};
+        };
+        peak_lists.reserve(4 * n);  // the accumulators point into these
+        windows.reserve(2 * n);
+        for (size_t j = 0; j < n; ++j) {
+            before.push_back(msa());
+            expected.push_back(msa());
+            add_off.push_back(add_off.back() + g.below(10));
+            const size_t m = g.below(7), r0 = (size_t)rec_off.back();
+            for (size_t r = 0; r < m; ++r) {
+                if (r && g.below(3) == 0) {  // an earlier record's whole index array again
+                    const size_t src = r0 + g.below(r);
+                    minimum.push_back(minimum[2 * src]);
+                    minimum.push_back(minimum[2 * src + 1]);
+                    for (size_t t = 0; t < 45; ++t) distances.push_back(distances[45 * src + t]);
+                } else {
+                    uint64_t lo = 2048 * half_chunk - 1 - g.below(12), hi = 0;
+                    if (special == HIGH_WORD) hi = 1 + g.below(3);
+                    if (special == CROSS_2_64) lo = ~0ull - g.below(12);  // minimum + distance carries into the high word
+                    minimum.push_back(lo);
+                    minimum.push_back(hi);
+                    for (size_t t = 0; t < 45; ++t) distances.push_back((uint32_t)(g.below(16) + (g.below(8) ? 0 : 4096)));
+                }
+                const size_t entries = g.below(4);
+                for (size_t e = 0; e < entries; ++e) {
+                    chunk_index.push_back(g.below(9));
+                    const size_t pd = g.below(3), rw = g.below(4);
+                    for (size_t q = 0; q < 5 * pd; ++q) path.push_back(g.next());
+                    for (size_t q = 0; q < rw; ++q) rel.push_back((uint32_t)g.below(4096));
+                    path_off.push_back(path_off.back() + pd);
+                    rel_off.push_back(rel_off.back() + rw);
+                }
+                entry_off.push_back(entry_off.back() + entries);
+            }
+            rec_off.push_back(r0 + m);
+            active_off.push_back(active_off.back() + before[j].n_active + 45 * m + g.below(4));
+        }
+        additions.assign(5 * (size_t)add_off.back(), 1);
+        verdict.resize(n);
+        status.resize(n);
+        bad_record.resize(n);
+        o_aocl.resize(n * 320);
+        o_swbf.resize(n * 320);
+        o_an.resize(n);
+        o_sn.resize(n);
+        o_nact.resize(n);
+        o_anp.resize(n);
+        o_snp.resize(n);
+        o_active.resize((size_t)active_off.back());
+        // every array exactly sized: a copy has no spare capacity
+        for (auto* v : {&add_off, &additions, &rec_off, &minimum, &entry_off, &chunk_index, &path_off, &path, &rel_off,
+                        &active_off})
+            *v = std::vector<uint64_t>(*v);
+        for (auto* v : {&distances, &rel}) *v = std::vector<uint32_t>(*v);
+        before = std::vector<nhip_msa>(before);
+        expected = std::vector<nhip_msa>(expected);
+    }
+    nhip_ms_apply_in in() {
+        chunks = nhip_ms_chunks{ptr(entry_off), ptr(chunk_index), ptr(path_off), ptr(path), ptr(rel_off), ptr(rel)};
+        return nhip_ms_apply_in{before.size(), ptr(before), ptr(add_off), ptr(additions), ptr(rec_off), ptr(minimum),
+                                ptr(distances), &chunks, with_expected ? ptr(expected) : nullptr};
+    }
+    nhip_ms_apply_out out() {
+        nhip_ms_apply_out o{};
+        o.verdict = ptr(verdict);
+        o.status = ptr(status);
+        o.bad_record = ptr(bad_record);
+        if (with_acc) {
+            o.aocl_peaks = ptr(o_aocl);
+            o.aocl_n_peaks = ptr(o_anp);
+            o.aocl_num_leafs = ptr(o_an);
+            o.swbf_peaks = ptr(o_swbf);
+            o.swbf_n_peaks = ptr(o_snp);
+            o.swbf_num_leafs = ptr(o_sn);
+            o.active_off = ptr(active_off);
+            o.active = ptr(o_active);
+            o.n_active = ptr(o_nact);
+        }
+        return o;
+    }
+};
 
 }  // namespace
 
@@ -173,6 +451,17 @@ int main() {
         in = b.in();
         in.chunks = nullptr;
         expect(ms_apply_ok(&in, &out, nullptr), NHIP_ERR_ARG, "chunks null with records");
+    }
+    for (const bool with_expected : {false, true})
+        for (const bool with_acc : {false, true}) {
+            Batch b;
+            b.with_expected = with_expected;
+            b.with_acc = with_acc;
+            check_order(b.in(), b.out(), "the fixed batch");
+        }
+    for (uint64_t seed = 0; seed < 200; ++seed) {
+        RandomBatch b(seed, seed == 7 ? HIGH_WORD : seed == 11 ? CROSS_2_64 : PLAIN);
+        check_order(b.in(), b.out(), "random batch " + std::to_string(seed));
     }
     std::printf("good %d bad %d\n", good, bad);
     return failures ? 1 : 0;

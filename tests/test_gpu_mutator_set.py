@@ -372,3 +372,37 @@ def test_empty_batches_zero_entries_and_bad_offsets(ctx, world):
     assert lib.nhip_mmr_verify_batch(h, ctypes.byref(cm.aocl), idx.ctypes.data, leaf.ctypes.data,
                                      np.asarray([0, 2, 3], dtype=np.uint64).ctypes.data, None, 2,
                                      v.ctypes.data) == L.NHIP_ERR_ARG
+
+
+# ---------------------------------------------------------------- 6. one workspace under every staged call
+def test_workspace_regrows_between_staged_calls_on_one_context(world):
+    """The host-buffer calls carve their device buffers out of one grow-only workspace per context (1 MiB at
+    first): small calls of different layouts, a call past 1 MiB that frees and regrows it (70,000 pairs,
+    3 x 2.8 MB), and small calls again on the regrown one, each against its oracle."""
+    import os
+
+    import coracle as C
+    import mast_ref as M
+    import neptune_hip as nh
+    import tip5_ref as T
+    from neptune_hip.mast import mast_hash_batch
+    from neptune_hip.mutator_set import can_remove_batch
+    rng = np.random.default_rng(77)
+    l1, r1 = (rng.integers(0, P, size=(1, 5), dtype=np.uint64) for _ in range(2))
+    want1 = [int(x) for x in T.hash_pair([int(x) for x in l1[0]], [int(x) for x in r1[0]])]
+    objs = [[[int(x) for x in rng.integers(0, P, size=int(rng.integers(0, 12)), dtype=np.uint64)] for _ in range(5)]
+            for _ in range(3)]
+    big_l, big_r = (rng.integers(0, P, size=(70000, 5), dtype=np.uint64) for _ in range(2))
+    live = [i for i in range(600) if i not in world.removed]
+    records = [world.arch.removal_record(i) for i in live[:6] + live[-6:] + world.removed[:12]]
+    want_rm = [R.can_remove(world.msa, rec) for rec in records]
+    assert {c for _, c, _ in want_rm} == {True, False}
+    with nh.Context(int(os.environ.get("LOCAL_RANK", "0"))) as c:  # a context of its own: its workspace starts unallocated
+        first = c.hash_pair(l1, r1)
+        assert [int(x) for x in first[0]] == want1
+        assert mast_hash_batch(c, objs) == [M.mast_hash(o) for o in objs]
+        big = c.hash_pair(big_l, big_r)
+        assert all((big[i] == C.hash_pair(big_l[i], big_r[i])).all() for i in range(70000))
+        assert can_remove_batch(c, to_msa(world.msa), [to_record(rec) for rec in records]) == want_rm
+        last = c.hash_pair(l1, r1)
+        assert (last == first).all() and [int(x) for x in last[0]] == want1
