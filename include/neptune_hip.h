@@ -580,6 +580,84 @@ int nhip_pow_validate_batch(nhip_ctx *ctx, uint32_t height, const uint64_t *root
                             const uint64_t *targets, const uint64_t *parents, const uint8_t *reboot_rules, size_t n,
                             uint8_t *verdicts);
 
+/* ---- block digests and the header chain ----------------------------------
+ * What `Block::validate` rules 0.a-0.g (block/mod.rs:726-782) and `Block::has_proof_of_work`
+ * (:920-942) read, and `Block::hash` (:189-195,317) for a batch of scanned blocks.
+ *
+ * nhip_blk_header (host only): one scanned block's header fields (canonical), the byte offsets of the
+ * pow's two authentication paths (pow_tree_height digests each), the block MMR accumulator of its body
+ * (mmr_n_peaks is the serialized peak count saturated at 65; at most 64 are stored) and, through
+ * `words`, the appendix's BFieldCodec encoding (appendix_words) followed by the words of the proof's
+ * BFieldCodec encoding that precede Proof.0's items (prefix_words: the BlockProof discriminant alone for
+ * Genesis and Invalid).  words == NULL: sizes only; else cap >= appendix_words + prefix_words. */
+typedef struct {
+    uint64_t version, height, timestamp;
+    uint64_t prev_block_digest[5];
+    uint64_t pow_root[5], pow_nonce[5];
+    uint64_t path_a_offset, path_b_offset;
+    uint32_t cumulative_proof_of_work[6];
+    uint32_t difficulty[5];
+    uint32_t mmr_n_peaks;
+    uint64_t receiver_digest[5], lock_script_hash[5];
+    uint64_t mmr_num_leafs;
+    uint64_t mmr_peaks[64][5];
+    uint64_t appendix_words, prefix_words;
+    uint64_t proof_offset, proof_len; /* SingleProof: Proof.0's first byte and its words, as this walk found them */
+} nhip_blk_header_out;
+int nhip_blk_header(const uint8_t *bytes, size_t n_bytes, uint32_t pow_tree_height, const nhip_blk_block *block,
+                    nhip_blk_header_out *out, uint64_t *words, size_t cap);
+/* Difficulty::target (difficulty_control.rs:69-76): (p^5 - 1) / difficulty as a digest, element 0 the
+ * lowest base-p digit (host only).  A zero difficulty (the reference panics) is NHIP_ERR_ARG. */
+int nhip_difficulty_target(const uint32_t difficulty[5], uint64_t target_out[5]);
+/* difficulty_control (difficulty_control.rs:441-486); timestamps and the interval in milliseconds, reduced
+ * mod p as Timestamp::millis does (host only).  A zero interval after a non-genesis parent (the reference
+ * panics) is NHIP_ERR_ARG. */
+int nhip_difficulty_control(uint64_t new_timestamp, uint64_t old_timestamp, const uint32_t old_difficulty[5],
+                            uint64_t target_block_interval, uint64_t previous_block_height,
+                            uint32_t difficulty_out[5]);
+
+/* Network parameters of the chain rules (application/config/network.rs:66-130,
+ * consensus_rule_set.rs:50-70) and the validator's clock. */
+typedef struct {
+    uint64_t minimum_block_time_ms, target_block_interval_ms;
+    uint64_t difficulty_reset_interval_ms;      /* 0: none */
+    uint32_t genesis_difficulty[5];
+    uint64_t hardfork_alpha_height;             /* first height under HardforkAlpha; 0: always */
+    uint64_t now_ms;
+    uint32_t pow_tree_height;
+    uint32_t allows_mock_pow;
+} nhip_chain_params;
+/* block_validation_error.rs:12-31, in rule order; the first rule that fails is the status */
+enum {
+    NHIP_LINK_OK = 0,
+    NHIP_LINK_SKIPPED = 1,             /* parent_of[i] == -1: nothing checked */
+    NHIP_LINK_BLOCK_HEIGHT = 2,        /* 0.a */
+    NHIP_LINK_PREV_BLOCK_DIGEST = 3,   /* 0.b */
+    NHIP_LINK_BLOCK_MMR_UPDATE = 4,    /* 0.c; also a parent accumulator whose peak count is not
+                                          popcount(num_leafs) or whose num_leafs is 2^64 - 1 (divergence:
+                                          the reference carries the former through `append`) */
+    NHIP_LINK_MINIMUM_BLOCK_TIME = 5,  /* 0.d */
+    NHIP_LINK_DIFFICULTY = 6,          /* 0.e */
+    NHIP_LINK_CUMULATIVE_POW = 7,      /* 0.f */
+    NHIP_LINK_FUTURE_DATING = 8        /* 0.g */
+};
+/* Block::hash of n scanned blocks (blocks[i] from nhip_blk_scan of the same bytes with the same
+ * pow_tree_height <= 32; each is parsed again, a malformed one is NHIP_ERR_DECODE): the body MAST hashes
+ * as nhip_mast_hash_batch gives them, the proof encodings absorbed from the raw bytes on the device
+ * (k_block_proof_leaf), the header / kernel / block MASTs (k_block_masts).  mast_out (nullable): the
+ * PowMastPaths of each block (block/mod.rs:946-962), with which fast_mast_hash (pow.rs:219-241)
+ * reproduces digests_out.  bytes is DMA'd as it lies when pinned, else staged (as nhip_le_words_gpu). */
+int nhip_blk_digests(nhip_ctx *ctx, const uint8_t *bytes, size_t n_bytes, uint32_t pow_tree_height,
+                     const nhip_blk_block *blocks, size_t n, uint64_t *digests_out, nhip_pow_mast_paths *mast_out);
+/* Rules 0.a-0.g for every (blocks[parent_of[i]], blocks[i]) pair, then has_proof_of_work of blocks[i]
+ * against that parent's header into pow_ok (1 / 0; 0 for a skipped pair), whatever link_status is.
+ * The rule set of Pow::validate is Reboot below params->hardfork_alpha_height (the height after the
+ * parent's, as mod.rs:939-940) and HardforkAlpha from it on.  A parent index outside -1..n-1 is
+ * NHIP_ERR_ARG; a HIP error is NHIP_ERR_HIP / NHIP_ERR_OOM, never a status byte. */
+int nhip_blk_chain_check(nhip_ctx *ctx, const uint8_t *bytes, size_t n_bytes, const nhip_chain_params *params,
+                         const nhip_blk_block *blocks, size_t n, const int64_t *parent_of, uint8_t *link_status,
+                         uint8_t *pow_ok, uint64_t *digests_out);
+
 /* ---- MAST and mutator-set hashing ----------------------------------
  * MastHash::mast_hash (neptune-core/src/protocol/proof_abstractions/mast_hash.rs:22-39) of n
  * objects with `fields` (1..16) field sequences each (TransactionKernel: 8): sequence (i, f) =

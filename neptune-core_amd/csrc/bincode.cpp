@@ -32,6 +32,17 @@
 // u64 / u128 as u32 limbs low first [EXT, unpinned].  The test restatement is
 // oracle/bincode_ref.py.
 //
+// The header chain (nhip_blk_header).  BlockHeader's MAST sequences (block_header.rs:204-215)
+// are the BFieldCodec encodings of its eight fields: version, height, timestamp one word each, prev_block_digest
+// five, pow.encode() = nonce ++ path_b ++ path_a ++ root (pow.rs:196-197; static sizes, no prefix),
+// cumulative_proof_of_work six and difficulty five u32 limbs in array order, guesser_receiver_data =
+// lock_script_hash ++ receiver_digest.  BlockKernel's (block_kernel.rs:112-119): header and body MAST hashes,
+// then appendix.encode().  Block's (block/mod.rs:192-194): the kernel MAST hash, then proof.encode().  Pin
+// status: the reversed field order and Claim's layout are pinned (pow.rs:196-197, new_claim.rs:38-100);
+// BlockAppendix { claims } = [len] + Vec<Claim> with each claim length-prefixed, and the derived enum BlockProof
+// = [variant index] + its fields (SingleProof's Proof length-prefixed, Proof = [n + 1, n, items]) follow
+// bfieldcodec_derive's rules for structs and enums [EXT, unpinned].
+//
 // Everything is host code: parsing is byte-serial and a few hundred MB/s per thread is far above
 // what a verifier batch consumes.
 #include <algorithm>
@@ -40,6 +51,7 @@
 #include <vector>
 
 #include "../../include/neptune_hip.h"
+#include "chain_rules.hpp"
 
 namespace {
 constexpr uint64_t P = 0xFFFFFFFF00000001ull;
@@ -406,6 +418,119 @@ int nhip_blk_claims(const uint8_t* bytes, size_t n_bytes, const nhip_blk_block* 
     return NHIP_OK;
 }
 
+// One walk of the block at `offset` for what the chain rules and Block::hash read (header comment: "header
+// chain"): *out, and the appendix encoding followed by the proof encoding's prefix appended to w (w is left as it
+// was on a decode error).  May throw std::bad_alloc.
+static int blk_header_walk(const uint8_t* bytes, size_t n_bytes, uint32_t pow_tree_height, uint64_t offset,
+                           nhip_blk_header_out* out, std::vector<uint64_t>& w) {
+    Rd r{bytes, n_bytes, (size_t)offset};
+    std::memset(out, 0, sizeof(*out));
+    out->version = r.bfe();
+    out->height = r.bfe();
+    r.digest(out->prev_block_digest);
+    out->timestamp = r.bfe();
+    r.digest(out->pow_root);
+    out->path_a_offset = r.o;
+    r.skip(40ull * pow_tree_height);
+    out->path_b_offset = r.o;
+    r.skip(40ull * pow_tree_height);
+    r.digest(out->pow_nonce);
+    for (int i = 0; i < 6; ++i) out->cumulative_proof_of_work[i] = r.u32();
+    for (int i = 0; i < 5; ++i) out->difficulty[i] = r.u32();
+    r.digest(out->receiver_digest);
+    r.digest(out->lock_script_hash);
+    size_t k_ends[8];
+    tx_kernel(r, nullptr, k_ends);
+    mmr_accumulator(r, nullptr);  // aocl
+    mmr_accumulator(r, nullptr);  // swbf_inactive
+    vec_u32(r, nullptr);          // swbf_active
+    mmr_accumulator(r, nullptr);  // lock_free_mmr_accumulator
+    out->mmr_num_leafs = r.u64();  // block_mmr_accumulator
+    const uint64_t np = r.len(40);
+    out->mmr_n_peaks = (uint32_t)std::min<uint64_t>(np, 65);
+    for (uint64_t i = 0; i < np && r.ok; ++i) {
+        uint64_t d[5];
+        r.digest(d);
+        if (i < 64) std::memcpy(out->mmr_peaks[i], d, 40);
+    }
+    // BlockAppendix { claims: Vec<Claim> }: [len] + ([n] + per claim [len] + Claim), Claim last-first
+    // (new_claim.rs:38-100): output, input (each [len + 1, len, items]), version, program_digest
+    Em e;
+    e.w.swap(w);  // append to the caller's words
+    const size_t w0 = e.w.size();
+    const size_t m_field = e.mark();
+    const uint64_t nc = r.len(40 + 4 + 16);
+    e.put(nc);
+    for (uint64_t i = 0; i < nc && r.ok; ++i) {
+        uint64_t pd[5];
+        r.digest(pd);
+        const uint32_t version = r.u32();
+        Em in;
+        vec_bfe(r, &in);
+        const size_t m_claim = e.mark();
+        const size_t m_out = e.mark();
+        vec_bfe(r, &e);
+        e.close(m_out);
+        e.put(in.w.size());
+        e.w.insert(e.w.end(), in.w.begin(), in.w.end());
+        e.put(version);
+        for (int q = 0; q < 5; ++q) e.put(pd[q]);
+        e.close(m_claim);
+    }
+    e.close(m_field);
+    out->appendix_words = e.w.size() - w0;
+    // BlockProof (derived enum): [discriminant], then SingleProof's field Proof(Vec<BFieldElement>),
+    // dynamic, so prefixed: [n + 2], Proof = [n + 1] + Vec = [n] + items
+    const uint32_t kind = r.variant(3);
+    e.put(kind);
+    if (r.ok && kind == NHIP_BLOCK_PROOF_SINGLE) {
+        const uint64_t n = r.len(8);
+        e.put(n + 2);
+        e.put(n + 1);
+        e.put(n);
+        out->proof_offset = r.o;
+        out->proof_len = n;
+        r.skip(8 * n);
+    }
+    e.w.swap(w);
+    if (!r.ok) {
+        w.resize(w0);
+        return NHIP_ERR_DECODE;
+    }
+    out->prefix_words = w.size() - w0 - out->appendix_words;
+    return NHIP_OK;
+}
+
+int nhip_blk_header(const uint8_t* bytes, size_t n_bytes, uint32_t pow_tree_height, const nhip_blk_block* block,
+                    nhip_blk_header_out* out, uint64_t* words, size_t cap) {
+    if (!bytes || !block || !out || block->offset > n_bytes || pow_tree_height > 64) return NHIP_ERR_ARG;
+    try {
+        std::vector<uint64_t> w;
+        const int rc = blk_header_walk(bytes, n_bytes, pow_tree_height, block->offset, out, w);
+        if (rc) return rc;
+        if (!words) return NHIP_OK;  // size query
+        if (cap < w.size()) return NHIP_ERR_ARG;
+        std::memcpy(words, w.data(), w.size() * 8);
+        return NHIP_OK;
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+int nhip_difficulty_target(const uint32_t difficulty[5], uint64_t target_out[5]) {
+    if (!difficulty || !target_out) return NHIP_ERR_ARG;
+    return nhip::chain::difficulty_target(difficulty, target_out) ? NHIP_OK : NHIP_ERR_ARG;
+}
+
+int nhip_difficulty_control(uint64_t new_timestamp, uint64_t old_timestamp, const uint32_t old_difficulty[5],
+                            uint64_t target_block_interval, uint64_t previous_block_height, uint32_t difficulty_out[5]) {
+    if (!old_difficulty || !difficulty_out) return NHIP_ERR_ARG;
+    return nhip::chain::difficulty_control(new_timestamp % P, old_timestamp % P, old_difficulty, target_block_interval % P,
+                                           previous_block_height % P, difficulty_out)
+               ? NHIP_OK
+               : NHIP_ERR_ARG;
+}
+
 int nhip_le_words(const uint8_t* bytes, size_t n_bytes, uint64_t offset, size_t n, uint64_t* out) {
     if ((n && (!bytes || !out)) || offset > n_bytes || n > (n_bytes - offset) / 8) return NHIP_ERR_ARG;
     for (size_t i = 0; i < n; ++i) out[i] = rd_word(bytes + offset + 8 * i);
@@ -528,6 +653,29 @@ bool tx_proof_spans(const uint8_t* bytes, size_t n, std::vector<uint64_t>& spans
     if (!parse_tx(r, &t, nullptr, ends, spans.data() + base, nullptr)) return false;
     size = t.size;
     return true;
+}
+
+// chain_capi.hip's host decode, one walk each per block: nhip_blk_header's fields with its words appended to w,
+// and nhip_blk_sequences' words (replacing `words`, whose capacity is reused) and offsets.  May throw
+// std::bad_alloc.
+int blk_header_append(const uint8_t* bytes, size_t n_bytes, uint32_t pow_tree_height, uint64_t offset,
+                      nhip_blk_header_out* out, std::vector<uint64_t>& w) {
+    return blk_header_walk(bytes, n_bytes, pow_tree_height, offset, out, w);
+}
+int blk_sequences_into(const uint8_t* bytes, size_t n_bytes, uint32_t pow_tree_height, uint64_t offset,
+                       std::vector<uint64_t>& words, uint64_t offsets[12]) {
+    Rd r{bytes, n_bytes, (size_t)offset};
+    Em e;
+    e.w.swap(words);
+    e.w.clear();
+    size_t ends[11];
+    nhip_blk_block b;
+    const bool ok = parse_block(r, pow_tree_height, b, &e, ends);
+    e.w.swap(words);
+    if (!ok) return NHIP_ERR_DECODE;
+    offsets[0] = 0;
+    for (int i = 0; i < 11; ++i) offsets[i + 1] = ends[i];
+    return NHIP_OK;
 }
 }  // namespace nhip
 

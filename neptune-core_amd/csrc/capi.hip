@@ -68,7 +68,9 @@ extern "C" {
 // 2500: the mutator-set checks (nhip_mmr, nhip_msa, nhip_ms_chunks, NHIP_MS_*, nhip_mmr_verify_batch,
 // nhip_ms_can_remove_batch, nhip_ms_verify_batch)
 // 2600: batched mutator-set updates (nhip_ms_apply_in, nhip_ms_apply_out, nhip_ms_apply_batch, four NHIP_MS_*)
-int nhip_abi_version(void) { return 2600; }
+// 2700: block digests and the header chain (nhip_blk_header, nhip_difficulty_target, nhip_difficulty_control,
+// nhip_chain_params, NHIP_LINK_*, nhip_blk_digests, nhip_blk_chain_check)
+int nhip_abi_version(void) { return 2700; }
 
 int nhip_set_fs_form(int form) { return nhip::set_fs_form(form) == 0 ? NHIP_OK : NHIP_ERR_ARG; }
 int nhip_set_climb_from_ops(int64_t ops) { return nhip::set_climb_from_ops(ops) == 0 ? NHIP_OK : NHIP_ERR_ARG; }

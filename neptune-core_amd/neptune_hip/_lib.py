@@ -83,6 +83,37 @@ class BlkBlock(ctypes.Structure):
                 ("claim_words", ctypes.c_uint64), ("seq_words", ctypes.c_uint64)]
 
 
+class BlkHeader(ctypes.Structure):
+    """nhip_blk_header_out: what the chain rules and Block::hash read of one scanned block."""
+    _fields_ = [("version", ctypes.c_uint64), ("height", ctypes.c_uint64), ("timestamp", ctypes.c_uint64),
+                ("prev_block_digest", ctypes.c_uint64 * 5), ("pow_root", ctypes.c_uint64 * 5),
+                ("pow_nonce", ctypes.c_uint64 * 5), ("path_a_offset", ctypes.c_uint64),
+                ("path_b_offset", ctypes.c_uint64), ("cumulative_proof_of_work", ctypes.c_uint32 * 6),
+                ("difficulty", ctypes.c_uint32 * 5), ("mmr_n_peaks", ctypes.c_uint32),
+                ("receiver_digest", ctypes.c_uint64 * 5), ("lock_script_hash", ctypes.c_uint64 * 5),
+                ("mmr_num_leafs", ctypes.c_uint64), ("mmr_peaks", (ctypes.c_uint64 * 5) * 64),
+                ("appendix_words", ctypes.c_uint64), ("prefix_words", ctypes.c_uint64),
+                ("proof_offset", ctypes.c_uint64), ("proof_len", ctypes.c_uint64)]
+
+
+class ChainParams(ctypes.Structure):
+    """nhip_chain_params: the network's chain-rule parameters and the validator's clock."""
+    _fields_ = [("minimum_block_time_ms", ctypes.c_uint64), ("target_block_interval_ms", ctypes.c_uint64),
+                ("difficulty_reset_interval_ms", ctypes.c_uint64), ("genesis_difficulty", ctypes.c_uint32 * 5),
+                ("hardfork_alpha_height", ctypes.c_uint64), ("now_ms", ctypes.c_uint64),
+                ("pow_tree_height", ctypes.c_uint32), ("allows_mock_pow", ctypes.c_uint32)]
+
+
+class PowMastPaths(ctypes.Structure):
+    """nhip_pow_mast_paths: canonical digests."""
+    _fields_ = [("pow", (ctypes.c_uint64 * 5) * 3), ("header", (ctypes.c_uint64 * 5) * 2),
+                ("kernel", (ctypes.c_uint64 * 5) * 1)]
+
+
+NHIP_LINK_OK, NHIP_LINK_SKIPPED, NHIP_LINK_BLOCK_HEIGHT, NHIP_LINK_PREV_BLOCK_DIGEST, NHIP_LINK_BLOCK_MMR_UPDATE, \
+    NHIP_LINK_MINIMUM_BLOCK_TIME, NHIP_LINK_DIFFICULTY, NHIP_LINK_CUMULATIVE_POW, NHIP_LINK_FUTURE_DATING = range(9)
+
+
 class Tx(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint64), ("kind", ctypes.c_uint32), ("n_proofs", ctypes.c_uint32),
                 ("n_lock_scripts", ctypes.c_uint32), ("n_type_scripts", ctypes.c_uint32),
@@ -256,6 +287,13 @@ SIGNATURES = {
     "nhip_blk_scan": ([_vp, _sz, ctypes.c_uint32, _vp, _sz, ctypes.POINTER(_sz)], ctypes.c_int),
     "nhip_blk_sequences": ([_vp, _sz, ctypes.c_uint32, ctypes.POINTER(BlkBlock), _vp, _sz, _vp], ctypes.c_int),
     "nhip_blk_claims": ([_vp, _sz, ctypes.POINTER(BlkBlock), _vp, _vp], ctypes.c_int),
+    "nhip_blk_header": ([_vp, _sz, ctypes.c_uint32, ctypes.POINTER(BlkBlock), ctypes.POINTER(BlkHeader), _vp, _sz],
+                        ctypes.c_int),
+    "nhip_difficulty_target": ([_vp, _vp], ctypes.c_int),
+    "nhip_difficulty_control": ([ctypes.c_uint64, ctypes.c_uint64, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp],
+                                ctypes.c_int),
+    "nhip_blk_digests": ([_vp, _vp, _sz, ctypes.c_uint32, _vp, _sz, _vp, _vp], ctypes.c_int),
+    "nhip_blk_chain_check": ([_vp, _vp, _sz, ctypes.POINTER(ChainParams), _vp, _sz, _vp, _vp, _vp, _vp], ctypes.c_int),
     "nhip_le_words": ([_vp, _sz, ctypes.c_uint64, _sz, _vp], ctypes.c_int),
     "nhip_le_words_gpu": ([_vp, _vp, _sz, ctypes.POINTER(Span), _sz, _vp], ctypes.c_int),
     "nhip_wire_scan_txs": ([_vp, _sz, _sz, ctypes.POINTER(Span), _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz),

@@ -12,6 +12,8 @@ natively (csrc/bincode.cpp) straight into the verifier's inputs.
 * `TransferTransaction.from_bytes(data)` — protocol/peer/transfer_transaction.rs:31-47: the kernel's
   MAST sequences and the `TransactionProof` (SingleProof words or a `ProofCollection`), ready for
   `verifier.transactions_are_valid`.
+* `block_digests` / `chain_links` / `chain_params` — `Block::hash`, and `Block::validate` rules 0.a-0.g with
+  `Block::has_proof_of_work` for every (parent, child) pair of a file, each one call (DESIGN.md §6e).
 Proof words are copied once, reduced mod p, from the file bytes into numpy buffers that the
 verifier stages without further conversion, or, given an `arena` (`stark.Arena`, round 6), straight
 into pinned memory on a GPU's NUMA node (nhip_arena_ingest_blocks / _spans), from where the
@@ -139,6 +141,93 @@ def validate_block_file(ctx, path: str, verifier, programs, network=None,
     recs = blocks_from_file_without_record(path, pow_tree_height, arena)
     return validate_block_proofs(ctx, blocks_to_validate(ctx, recs), verifier, programs,
                                  network if network is not None else Network.MAIN)
+
+
+# application/config/network.rs:66-130 and consensus_rule_set.rs:9-14,50-70, per `verifier.Network`:
+# (minimum_block_time ms, target_block_interval ms, difficulty_reset_interval ms or 0, genesis difficulty limb 0,
+#  first HardforkAlpha height or 0 = always, allows_mock_pow)
+_CHAIN_RULES = {"main": (60_000, 588_000, 0, 100_000_000, 15_000, False),
+                "testnet": (60_000, 588_000, 0, 100_000, 120, False),
+                "testnet-mock": (100, 588_000, 2 * 588_000, 100_000, 0, False),
+                "regtest": (1, 100, 0, 6_000, 0, True)}
+LINK_OK, LINK_SKIPPED, LINK_BLOCK_HEIGHT, LINK_PREV_BLOCK_DIGEST, LINK_BLOCK_MMR_UPDATE, LINK_MINIMUM_BLOCK_TIME, \
+    LINK_DIFFICULTY, LINK_CUMULATIVE_POW, LINK_FUTURE_DATING = range(9)
+
+
+def chain_params(network, now: int, pow_tree_height: int = POW_TREE_HEIGHT) -> "_lib.ChainParams":
+    """The chain-rule parameters of `network` (a `verifier.Network`) and the validator's clock `now`
+    (a Timestamp: milliseconds), as `nhip_blk_chain_check` reads them."""
+    mn, target, reset, genesis, alpha, mock = _CHAIN_RULES[network.value]
+    p = _lib.ChainParams()
+    p.minimum_block_time_ms, p.target_block_interval_ms, p.difficulty_reset_interval_ms = mn, target, reset
+    p.genesis_difficulty[0] = genesis
+    p.hardfork_alpha_height, p.now_ms = alpha, int(now)
+    p.pow_tree_height, p.allows_mock_pow = pow_tree_height, 1 if mock else 0
+    return p
+
+
+def difficulty_target(difficulty: Sequence[int]) -> Tuple[int, ...]:
+    """`Difficulty::target` (difficulty_control.rs:69-76) of five u32 limbs, as a digest (host only)."""
+    d, out = np.array([int(x) for x in difficulty], dtype=np.uint32), np.zeros(5, dtype=np.uint64)
+    check(_lib.load().nhip_difficulty_target(d.ctypes.data, out.ctypes.data), "nhip_difficulty_target")
+    return tuple(int(x) for x in out)
+
+
+def difficulty_control(new_timestamp: int, old_timestamp: int, old_difficulty: Sequence[int], target_block_interval: int,
+                       previous_block_height: int) -> List[int]:
+    """`difficulty_control` (difficulty_control.rs:441-486); times in milliseconds (host only)."""
+    d, out = np.array([int(x) for x in old_difficulty], dtype=np.uint32), np.zeros(5, dtype=np.uint32)
+    check(_lib.load().nhip_difficulty_control(new_timestamp, old_timestamp, d.ctypes.data, target_block_interval,
+                                              previous_block_height, out.ctypes.data), "nhip_difficulty_control")
+    return [int(x) for x in out]
+
+
+def _scanned(records) -> "ctypes.Array":
+    """The records as `nhip_blk_block`s: the chain entry points walk each block again from its offset."""
+    blocks = (_lib.BlkBlock * max(len(records), 1))()
+    for b, r in zip(blocks, records):
+        b.offset, b.size = r.offset, r.size
+    return blocks
+
+
+def block_digests(ctx, data, records: Sequence[BlockRecord], pow_tree_height: int = POW_TREE_HEIGHT,
+                  with_mast_paths: bool = False):
+    """`Block::hash` (block/mod.rs:189-195,317) of every record of `data` in one call (`nhip_blk_digests`):
+    an (n, 5) uint64 array; with `with_mast_paths`, also each block's `PowMastPaths` (block/mod.rs:946-962)
+    as (pow 3, header 2, kernel 1) digest tuples."""
+    a, n = _buf(data)
+    m = len(records)
+    out = np.zeros((max(m, 1), 5), dtype=np.uint64)
+    mast = (_lib.PowMastPaths * max(m, 1))() if with_mast_paths else None
+    check(ctx.lib.nhip_blk_digests(ctx.handle, a.ctypes.data, n, pow_tree_height,
+                                   ctypes.cast(_scanned(records), ctypes.c_void_p), m, out.ctypes.data,
+                                   ctypes.cast(mast, ctypes.c_void_p) if with_mast_paths else None), "nhip_blk_digests")
+    if not with_mast_paths:
+        return out[:m]
+    dig = lambda d: tuple(int(x) for x in d)  # noqa: E731
+    return out[:m], [(tuple(dig(d) for d in p.pow), tuple(dig(d) for d in p.header), tuple(dig(d) for d in p.kernel))
+                     for p in mast[:m]]
+
+
+def chain_links(ctx, data, records: Sequence[BlockRecord], network, now: int, parent_of=None,
+                pow_tree_height: int = POW_TREE_HEIGHT, params=None) -> List[Tuple[int, bool]]:
+    """`Block::validate` rules 0.a-0.g and `Block::has_proof_of_work` (block/mod.rs:726-782,920-942) for every
+    (parent, child) pair of `records` in one call (`nhip_blk_chain_check`): `[(status, pow_ok)]` with `status`
+    one of `LINK_*`.  `parent_of[i]`: the record that is block i's parent, -1 to skip the pair; by default the
+    block before it in the file, and the first block is skipped.  `params`: a `ChainParams` instead of
+    `chain_params(network, now)`."""
+    a, n = _buf(data)
+    m = len(records)
+    par = np.arange(-1, m - 1, dtype=np.int64) if parent_of is None else np.asarray(parent_of, dtype=np.int64)
+    if par.shape != (m,):
+        raise ValueError("parent_of needs one entry per record")
+    par = np.ascontiguousarray(par) if m else np.zeros(1, dtype=np.int64)
+    p = params if params is not None else chain_params(network, now, pow_tree_height)
+    status, pow_ok = np.zeros(max(m, 1), dtype=np.uint8), np.zeros(max(m, 1), dtype=np.uint8)
+    check(ctx.lib.nhip_blk_chain_check(ctx.handle, a.ctypes.data, n, ctypes.byref(p),
+                                       ctypes.cast(_scanned(records), ctypes.c_void_p), m, par.ctypes.data,
+                                       status.ctypes.data, pow_ok.ctypes.data, None), "nhip_blk_chain_check")
+    return [(int(s), bool(k)) for s, k in zip(status[:m], pow_ok[:m])]
 
 
 def inputs_removable(ctx, msa_before, removal_records) -> Tuple[bool, Optional[int]]:

@@ -167,6 +167,55 @@ pub struct nhip_pow_mast_paths {
     pub kernel: [[u64; 5]; 1],
 }
 
+/// What the chain rules and `Block::hash` read of one scanned block (`nhip_blk_header`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_blk_header_out {
+    pub version: u64,
+    pub height: u64,
+    pub timestamp: u64,
+    pub prev_block_digest: [u64; 5],
+    pub pow_root: [u64; 5],
+    pub pow_nonce: [u64; 5],
+    pub path_a_offset: u64,
+    pub path_b_offset: u64,
+    pub cumulative_proof_of_work: [u32; 6],
+    pub difficulty: [u32; 5],
+    pub mmr_n_peaks: u32,
+    pub receiver_digest: [u64; 5],
+    pub lock_script_hash: [u64; 5],
+    pub mmr_num_leafs: u64,
+    pub mmr_peaks: [[u64; 5]; 64],
+    pub appendix_words: u64,
+    pub prefix_words: u64,
+    pub proof_offset: u64,
+    pub proof_len: u64,
+}
+
+/// The network's chain-rule parameters and the validator's clock (`nhip_blk_chain_check`).
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct nhip_chain_params {
+    pub minimum_block_time_ms: u64,
+    pub target_block_interval_ms: u64,
+    pub difficulty_reset_interval_ms: u64,
+    pub genesis_difficulty: [u32; 5],
+    pub hardfork_alpha_height: u64,
+    pub now_ms: u64,
+    pub pow_tree_height: u32,
+    pub allows_mock_pow: u32,
+}
+
+pub const NHIP_LINK_OK: u8 = 0;
+pub const NHIP_LINK_SKIPPED: u8 = 1;
+pub const NHIP_LINK_BLOCK_HEIGHT: u8 = 2;
+pub const NHIP_LINK_PREV_BLOCK_DIGEST: u8 = 3;
+pub const NHIP_LINK_BLOCK_MMR_UPDATE: u8 = 4;
+pub const NHIP_LINK_MINIMUM_BLOCK_TIME: u8 = 5;
+pub const NHIP_LINK_DIFFICULTY: u8 = 6;
+pub const NHIP_LINK_CUMULATIVE_POW: u8 = 7;
+pub const NHIP_LINK_FUTURE_DATING: u8 = 8;
+
 /// An MMR accumulator: `n_peaks` digests (tallest peak first) and the leaf count.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -357,6 +406,19 @@ extern "C" {
                               block: *const nhip_blk_block, words: *mut u64, cap: usize, offsets: *mut u64) -> c_int;
     pub fn nhip_blk_claims(bytes: *const u8, n_bytes: usize, block: *const nhip_blk_block, words: *mut u64,
                            claims: *mut nhip_claim) -> c_int;
+    pub fn nhip_blk_header(bytes: *const u8, n_bytes: usize, pow_tree_height: u32, block: *const nhip_blk_block,
+                           out: *mut nhip_blk_header_out, words: *mut u64, cap: usize) -> c_int;
+    pub fn nhip_difficulty_target(difficulty: *const u32, target_out: *mut u64) -> c_int;
+    pub fn nhip_difficulty_control(new_timestamp: u64, old_timestamp: u64, old_difficulty: *const u32,
+                                   target_block_interval: u64, previous_block_height: u64,
+                                   difficulty_out: *mut u32) -> c_int;
+    pub fn nhip_blk_digests(ctx: *mut nhip_ctx, bytes: *const u8, n_bytes: usize, pow_tree_height: u32,
+                            blocks: *const nhip_blk_block, n: usize, digests_out: *mut u64,
+                            mast_out: *mut nhip_pow_mast_paths) -> c_int;
+    pub fn nhip_blk_chain_check(ctx: *mut nhip_ctx, bytes: *const u8, n_bytes: usize,
+                                params: *const nhip_chain_params, blocks: *const nhip_blk_block, n: usize,
+                                parent_of: *const i64, link_status: *mut u8, pow_ok: *mut u8,
+                                digests_out: *mut u64) -> c_int;
     pub fn nhip_le_words(bytes: *const u8, n_bytes: usize, offset: u64, n: usize, out: *mut u64) -> c_int;
     pub fn nhip_le_words_gpu(ctx: *mut nhip_ctx, bytes: *const u8, n_bytes: usize, spans: *const nhip_span, n: usize,
                              out: *mut u64) -> c_int;
