@@ -82,12 +82,6 @@ __device__ __forceinline__ void st_xfe_raw(uint64_t* __restrict__ w, uint64_t of
     w[off + 1] = v.c1;
     w[off + 2] = v.c2;
 }
-__device__ __forceinline__ bool x_is_zero(Xfe a) { return (a.c0 | a.c1 | a.c2) == 0; }
-
-// primitive root of unity of order 2^k (raw Montgomery): 7^((p-1) / 2^k)
-__device__ __forceinline__ uint64_t root_of_unity(uint32_t log2n) {
-    return b_pow(to_mont(7), (GL_P - 1) >> log2n);
-}
 
 // ------------------------------------------------------------------ proof-stream decode
 // One wave per proof: lane 0 walks the proof stream (decode_stream, proof_codec.hpp: the item
@@ -1255,7 +1249,7 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 256 ? NHIP_OOD_WAVES : 1) k_oo
     // one inversion for the three (Montgomery's trick; a zero zerofier is flagged, stands in the
     // product as 1 and gets the inverse 0, as x_inv gives it), and the derived challenges on waves 1-3
     if (tid == 0) {
-        const uint64_t w_inv = b_inv(root_of_unity(d.log2_ph));
+        const uint64_t w_inv = root_of_unity_inv(d.log2_ph);
         const Xfe except_last = x_sub(z, x_lift(w_inv));
         const Xfe zm1 = x_sub(z, x_one());
         Xfe zph = z;
@@ -1401,18 +1395,11 @@ __global__ void __launch_bounds__(BLOCK, BLOCK == 256 ? NHIP_OOD_WAVES : 1) k_oo
 // One workgroup per proof.  Lane j follows collinearity check j through all rounds:
 // a_{r+1} = line through (x_a, a_r), (x_b, b_r) evaluated at alpha_r.  The round-r domain point of
 // check j is x_r = (7 * g^i)^(2^r) and its partner is -x_r (the a/b indices differ by half the
-// round-r domain), so one exponentiation and one inversion per lane serve every round:
+// round-r domain), so two powers of g per lane (x_0 and 1 / x_0 = g^(N - i) / 7) serve every round:
 // x_{r+1} = x_r^2, 1/x_{r+1} = (1/x_r)^2, slope = (b - a) * (-1/2) / x_r.  The lane also stores x_0
 // (raw) for DEEP.  Then the last codeword: agreement at the a-indices, and Horner(last polynomial, t)
 // == barycentric(last codeword, t).  The last codeword's Merkle tree is hashed with the multiproof
 // levels (k_mp_hash) and its root checked in k_mp_roots.
-__device__ __forceinline__ uint64_t lds_pow(const uint64_t* __restrict__ sq, uint64_t e) {
-    // sq[b] = g^(2^b); e < 2^32
-    uint64_t r = MONT_ONE;
-    for (uint32_t b = 0; e; ++b, e >>= 1)
-        if (e & 1) r = mont_mul(r, sq[b]);
-    return r;
-}
 
 #ifndef NHIP_FRI_WAVES
 #define NHIP_FRI_WAVES 1
@@ -1435,14 +1422,11 @@ __device__ __forceinline__ void fri_body(uint32_t p, const uint64_t* __restrict_
     const uint32_t* __restrict__ idx = idx_all + d.idx_off;
     const uint32_t L = d.last_cw_n;
     const uint32_t log2L = 31 - __clz(L);
-    if (tid == 0) {
-        lflag = 0;
-        uint64_t g = root_of_unity(d.log2_N);
-        for (uint32_t q = 0; q < d.log2_N; ++q, g = mont_mul(g, g)) gsq[q] = g;
-    } else if (tid == 64) {
-        uint64_t w = root_of_unity(log2L);
-        for (uint32_t q = 0; q < log2L; ++q, w = mont_mul(w, w)) wsq[q] = w;
-    }
+    // g^(2^q) for the root g of order 2^n is the root of order 2^(n - q): both tables straight from
+    // the two-adic roots, a lane per entry
+    if (tid == 0) lflag = 0;
+    if (tid < d.log2_N && tid < 33) gsq[tid] = root_of_unity(d.log2_N - tid);
+    if (tid < log2L) wsq[tid] = root_of_unity(log2L - tid);
     __syncthreads();
     uint32_t f = 0;
     if (tid < k) {
@@ -1450,7 +1434,9 @@ __device__ __forceinline__ void fri_body(uint32_t p, const uint64_t* __restrict_
         Xfe a = ld_xfe_w<MW>(words, d.fri[0].leaves_off + 3ull * tid);
         uint64_t x = mont_mul(to_mont(7), lds_pow(gsq, i0));
         xdom[(uint64_t)p * k + tid] = x;
-        uint64_t xinv = b_inv(x);
+        // 1 / (7 g^i) = 7^-1 g^(N - i): a power from the same table instead of an inversion (the
+        // exponent taken mod N = 2^log2_N in 32 bits, so log2_N = 32 keeps lds_pow's e < 2^32)
+        uint64_t xinv = mont_mul(SEVEN_INV, lds_pow(gsq, neg_mod_pow2(i0, d.log2_N)));
         const uint64_t neg_half = to_mont((GL_P - 1) / 2);  // -1/2
         for (uint32_t r = 0; r < d.R; ++r) {
             const Xfe b = ld_xfe_w<MW>(words, d.fri[1 + r].leaves_off + 3ull * tid);
@@ -1466,38 +1452,17 @@ __device__ __forceinline__ void fri_body(uint32_t p, const uint64_t* __restrict_
     // barycentric evaluation of the last codeword at the indeterminate vs Horner of the polynomial
     const Xfe t = ld_xfe_raw(xs, xb + 3ull * sl.indeterminate);
     Xfe num = x_zero(), den = x_zero();
-    if (tid < L) {
-        uint64_t wi = lds_pow(wsq, tid);
-        const uint64_t wstep = blockDim.x < L ? wsq[31 - __clz(blockDim.x)] : MONT_ONE;
-        // the lane's points two at a time with one inversion (Montgomery's trick: 1/d0 = d1 / (d0 d1));
-        // a zero difference (t on the domain: the proof is rejected either way) takes the one-at-a-time
-        // form, so num / den are those of the reference's per-point inverses in every case
-        auto term = [&](uint32_t i, uint64_t w, Xfe inv) {
-            const Xfe q = x_scale(inv, w);
-            num = x_add(num, x_mul(q, ld_xfe_w<MW>(words, d.last_cw_off + 3ull * i)));
-            den = x_add(den, q);
-        };
-        uint32_t i = tid;
-        for (; i + blockDim.x < L; i += 2 * blockDim.x) {
-            const uint64_t w1 = mont_mul(wi, wstep);
-            const Xfe d0 = x_sub(t, x_lift(wi)), d1 = x_sub(t, x_lift(w1));
-            const Xfe pr = x_mul(d0, d1);
-            if (x_is_zero(pr)) {
-                atomicOr(&lflag, 1u);
-                term(i, wi, x_inv(d0));
-                term(i + blockDim.x, w1, x_inv(d1));
-            } else {
-                const Xfe inv = x_inv(pr);
-                term(i, wi, x_mul(inv, d1));
-                term(i + blockDim.x, w1, x_mul(inv, d0));
-            }
-            wi = mont_mul(w1, wstep);
-        }
-        if (i < L) {
-            const Xfe diff = x_sub(t, x_lift(wi));
-            if (x_is_zero(diff)) atomicOr(&lflag, 1u);
-            term(i, wi, x_inv(diff));
-        }
+    {
+        // the codeword's points on as few waves as it allows (bary_slot, xfe.hpp: up to BARY_PPL_MAX
+        // points per lane behind one inversion); L is a power of two, so the S = L / ppl slots step by
+        // w^S, the root of order ppl.  A zero difference (t on the domain) only flags: the proof is
+        // rejected with FAIL_ZERO_INVERSE before num / den are looked at.  The slots go to the
+        // workgroup's last lanes, so the chain runs beside the check lanes' waves, not after them.
+        const uint32_t ppl = bary_points_per_lane(L), S = (L + ppl - 1) / ppl;
+        const uint64_t wS = root_of_unity(31 - __clz(ppl));
+        auto cw = [&](uint32_t i) { return ld_xfe_w<MW>(words, d.last_cw_off + 3ull * i); };
+        for (uint32_t s = blockDim.x - 1 - tid; s < S; s += blockDim.x)
+            if (bary_slot(t, lds_pow(wsq, s), wS, s, S, L, ppl, cw, num, den)) atomicOr(&lflag, 1u);
     }
     const Xfe snum = block_sum_xfe(num, red);
     const Xfe sden = block_sum_xfe(den, red);
@@ -1645,6 +1610,18 @@ __global__ void __launch_bounds__(256, NHIP_DEEP_WAVES) k_deep_rows8(const uint6
         o[3] = w_limbs(gl_sub(0, w2)), o[4] = w_limbs(gl_add(w0, w2)), o[5] = w_limbs(w1);
         o[6] = w_limbs(gl_sub(0, w1)), o[7] = w_limbs(gl_sub(w1, w2)), o[8] = w_limbs(gl_add(w0, w2));
     }
+    // quotient segments, a row per lane, before the row passes and beside the last wave's s_at (inside
+    // the pass loop the one lane in eight that took them cost every wave Q products in every pass):
+    // sum_q w_q * seg_q; Montgomery products of the raw weights with canonical words are canonical
+    // values (to_mont makes them raw), with Montgomery words raw already
+    for (uint32_t j = tid; j < k; j += blockDim.x) {
+        Xfe qv = x_zero();
+        for (uint32_t q = 0; q < Q; ++q)
+            qv = x_add(qv, x_mul(ld_xfe_raw(lw, 3ull * (M + A + q)),
+                                 ld_xfe_raw(words, d.quot_rows_off + (uint64_t)j * 3 * Q + 3ull * q)));
+        if constexpr (MW) s_quot[j] = qv;
+        else s_quot[j] = {to_mont(qv.c0), to_mont(qv.c1), to_mont(qv.c2)};
+    }
     if (tid == blockDim.x - 1) {
         const Xfe z = ld_xfe_raw(xs, xb + 3ull * sl.z);
         s_at[0] = z;
@@ -1724,16 +1701,6 @@ __global__ void __launch_bounds__(256, NHIP_DEEP_WAVES) k_deep_rows8(const uint6
             // canonical words: R * sum w x, the raw word; Montgomery words: R^2 * sum w x, one reduction
             if constexpr (MW) rowsum[j] = {from_mont(v0), from_mont(v1), from_mont(v2)};
             else rowsum[j] = {v0, v1, v2};
-        }
-        if (j < k && q8 == 1) {
-            // quotient segments: sum_q w_q * seg_q; Montgomery products of the raw weights with canonical
-            // words are canonical values (to_mont makes them raw), with Montgomery words raw already
-            Xfe qv = x_zero();
-            for (uint32_t q = 0; q < Q; ++q)
-                qv = x_add(qv, x_mul(ld_xfe_raw(lw, 3ull * (M + A + q)),
-                                     ld_xfe_raw(words, d.quot_rows_off + (uint64_t)j * 3 * Q + 3ull * q)));
-            if constexpr (MW) s_quot[j] = qv;
-            else s_quot[j] = {to_mont(qv.c0), to_mont(qv.c1), to_mont(qv.c2)};
         }
     }
     __syncthreads();

@@ -149,6 +149,51 @@ __host__ __device__ __forceinline__ uint64_t b_pow(uint64_t a, uint64_t e) {
     return r;
 }
 
+// The two-adic roots of unity 7^((p-1) >> k), k = 0..32 (order 2^k), and their inverses, as raw
+// Montgomery words, made at compile time with plain 128-bit integer arithmetic (tests/native/
+// aux_chain_check.cpp compares every entry with b_pow / b_inv).  Squaring walks down the table:
+// root[k]^2 == root[k - 1].
+namespace two_adic {
+constexpr uint64_t mulp(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a * b) % GL_P); }
+constexpr uint64_t powp(uint64_t a, uint64_t e) {
+    uint64_t r = 1;
+    for (; e; e >>= 1, a = mulp(a, a))
+        if (e & 1) r = mulp(r, a);
+    return r;
+}
+constexpr uint64_t raw(uint64_t x) { return (uint64_t)(((unsigned __int128)x << 64) % GL_P); }
+struct Roots {
+    uint64_t root[33], inv[33];
+};
+constexpr Roots make() {
+    Roots t{};
+    for (int k = 0; k <= 32; ++k) {
+        const uint64_t r = powp(7, (GL_P - 1) >> k);
+        t.root[k] = raw(r);
+        t.inv[k] = raw(powp(r, GL_P - 2));
+    }
+    return t;
+}
+}  // namespace two_adic
+static constexpr two_adic::Roots TWO_ADIC_ROOTS = two_adic::make();
+static constexpr uint64_t SEVEN_INV = two_adic::raw(two_adic::powp(7, GL_P - 2));  // raw word of 1 / 7
+
+// primitive root of unity of order 2^k (raw Montgomery), k <= 32, and its inverse
+__host__ __device__ __forceinline__ uint64_t root_of_unity(uint32_t log2n) { return TWO_ADIC_ROOTS.root[log2n]; }
+__host__ __device__ __forceinline__ uint64_t root_of_unity_inv(uint32_t log2n) { return TWO_ADIC_ROOTS.inv[log2n]; }
+
+// g^e from the table sq[b] = g^(2^b); e < 2^32
+__host__ __device__ __forceinline__ uint64_t lds_pow(const uint64_t* __restrict__ sq, uint64_t e) {
+    uint64_t r = MONT_ONE_W;
+    for (uint32_t b = 0; e; ++b, e >>= 1)
+        if (e & 1) r = mont_mul(r, sq[b]);
+    return r;
+}
+// (N - i) mod N for N = 2^log2_N <= 2^32, in 32 bits: the exponent of 1 / g^i for g of order N
+__host__ __device__ __forceinline__ uint32_t neg_mod_pow2(uint32_t i, uint32_t log2_N) {
+    return (0u - i) & (log2_N >= 32 ? ~0u : (1u << log2_N) - 1u);
+}
+
 // Inverse via the adjugate of the multiplication matrix (first row of cofactors / determinant).
 // Returns zero for zero (caller checks).
 __host__ __device__ __forceinline__ Xfe x_inv(Xfe a) {
@@ -170,6 +215,57 @@ __host__ __device__ __forceinline__ Xfe x_pow(Xfe a, uint64_t e) {
         e >>= 1;
     }
     return r;
+}
+
+__host__ __device__ __forceinline__ bool x_is_zero(Xfe a) { return (a.c0 | a.c1 | a.c2) == 0; }
+
+// Barycentric sum over a codeword of L points on the order-L subgroup, several points per lane:
+// num += sum_i f_i w^i / (t - w^i), den += sum_i w^i / (t - w^i).  The points are dealt to
+// S = ceil(L / ppl) slots, slot s taking s, s + S, s + 2S, ... (< L), and a slot inverts the product
+// of its differences once (Montgomery's trick: 3 products per further point instead of an
+// inversion).  ppl is chosen so that a codeword of up to 64 * BARY_PPL_MAX points takes one wave,
+// and a small one a point per lane.  A zero difference (t on the domain) is reported and stands in
+// the chain as 1; the caller rejects the proof without looking at num / den.
+static constexpr uint32_t BARY_PPL_MAX = 8;
+__host__ __device__ __forceinline__ uint32_t bary_points_per_lane(uint32_t L) {
+    uint32_t ppl = 1;
+    while (ppl < BARY_PPL_MAX && (L + ppl - 1) / ppl > 64) ppl *= 2;
+    return ppl;
+}
+// w0 = w^s, wS = w^S, ppl <= BARY_PPL_MAX; cw(i) is the codeword's value at w^i (i < L).  Returns
+// the zero flag.
+template <typename Cw>
+__host__ __device__ __forceinline__ bool bary_slot(Xfe t, uint64_t w0, uint64_t wS, uint32_t s, uint32_t S, uint32_t L,
+                                                   uint32_t ppl, Cw cw, Xfe& num, Xfe& den) {
+    // The two loops stay rolled (one copy of the four products: unrolled, 32 inlined x_mul are
+    // ~40 KB of code), so the per-point values are indexed at run time and live in the lane's
+    // private memory: 7 stores and loads of an XFE per chain beside ~5,000 VALU instructions.
+    uint64_t wv[BARY_PPL_MAX];
+    Xfe pre[BARY_PPL_MAX];  // product of the differences before point j
+    bool zero = false;
+    Xfe acc = x_one();
+    uint64_t w = w0;
+    uint32_t n = 0;
+#pragma unroll 1
+    for (; n < ppl && n < BARY_PPL_MAX && s + (uint64_t)n * S < L; ++n) {
+        Xfe df = x_sub(t, x_lift(w));
+        if (x_is_zero(df)) zero = true, df = x_one();
+        wv[n] = w;
+        pre[n] = acc;
+        acc = n ? x_mul(acc, df) : df;
+        w = mont_mul(w, wS);
+    }
+    Xfe inv = x_inv(acc);  // 1 / (the differences up to the point in hand), walking back
+#pragma unroll 1
+    for (uint32_t j = n; j-- > 0;) {
+        Xfe df = x_sub(t, x_lift(wv[j]));
+        if (x_is_zero(df)) df = x_one();
+        const Xfe q = x_scale(j ? x_mul(inv, pre[j]) : inv, wv[j]);
+        if (j) inv = x_mul(inv, df);
+        num = x_add(num, x_mul(q, cw(s + j * S)));
+        den = x_add(den, q);
+    }
+    return zero;
 }
 
 }  // namespace nhip
