@@ -719,7 +719,18 @@ enum {
                                       index, or num_leafs + additions wraps */
     NHIP_MS_DUPLICATE_RECORD = 7,  /* Block::validate 2.c: two records with equal index arrays */
     NHIP_MS_UPDATE_IMPOSSIBLE = 8, /* 2.d: a record whose indices are all set once the earlier ones are applied */
-    NHIP_MS_UPDATE_MISMATCH = 9    /* 2.e: the accumulator after is not the expected one */
+    NHIP_MS_UPDATE_MISMATCH = 9,   /* 2.e: the accumulator after is not the expected one */
+    /* packed removal records (rule 2.a, below): RemovalRecordList::try_unpack's errors, in the reference's order */
+    NHIP_MS_UNPACK_PAYLOAD_TOO_BIG = 10,          /* ChunkUnpackError::PayloadTooBig */
+    NHIP_MS_UNPACK_INCONSISTENT_LENGTH = 11,      /* ChunkUnpackError::InconsistentLength */
+    NHIP_MS_UNPACK_NONZERO_TRAILING_PADDING = 12, /* ChunkUnpackError::NonzeroTrailingPadding */
+    NHIP_MS_UNPACK_ILLEGAL_TREE_HEIGHT = 13,      /* RemovalRecordListUnpackError::IllegalTreeHeight */
+    NHIP_MS_UNPACK_DUPLICATE_TREE_HEIGHTS = 14,   /* ...::DuplicateTreeHeights */
+    NHIP_MS_UNPACK_INDEX_TOO_BIG = 15,            /* ...::AbsoluteIndexTooBig */
+    NHIP_MS_UNPACK_INCONSISTENT_CHUNKS = 16,      /* RemovalRecordListInconsistency::Chunks */
+    NHIP_MS_UNPACK_STRUCTURE_COUNT = 17,          /* ...::AuthenticationStructureCount */
+    NHIP_MS_UNPACK_STRUCTURE_LENGTH = 18,         /* ...::AuthenticationStructureLength */
+    NHIP_MS_UNPACK_PANIC = 19                     /* the reference panics on this list: fail closed */
 };
 /* twenty-first MmrMembershipProof::verify(leaf_index, leaf, peaks, num_leafs) for n (leaf, path)
  * items against one MMR, as called bare in application/loops/peer_loop.rs:1235 and
@@ -797,6 +808,45 @@ typedef struct {
     uint64_t *n_active;           /* n_jobs */
 } nhip_ms_apply_out;
 int nhip_ms_apply_batch(nhip_ctx *ctx, const nhip_ms_apply_in *in, nhip_ms_apply_out *out);
+
+/* ---- packed removal records: Block::validate rule 2.a --------------------------
+ * RemovalRecordList::try_unpack (util_types/mutator_set/removal_record/removal_record_list.rs:653-658,
+ * block/mod.rs:811-813) for n_jobs independent packed lists.  A packed list is a Vec<RemovalRecord>, so the input
+ * has the shapes above: job j is the records rec_off[j] .. rec_off[j + 1] (minimum, distances), and in `packed`
+ * chunk_index holds an entry's key (a tree height, a tree height + 64, or UINT64_MAX), path its authentication
+ * structure and rel its chunk's packed words (chunk.rs:148-194).  The output is the unpacked dictionaries of all
+ * records, a valid nhip_ms_chunks for the calls above; the records of a job that fails own no entry.  Per job the
+ * status is the first failure in the reference's own order, NHIP_MS_OK otherwise; every status is an integer
+ * decision of the host plan, and the path digests are computed on the device.  Divergence, failing closed:
+ * where the reference panics (heights not ascending in dictionary order, an estimate 8 s + 1 past u64, a
+ * structure that does not fit its own tree, a sibling missing while a path is read) the status is
+ * NHIP_MS_UNPACK_PANIC.
+ * Two-call sizing, as nhip_blk_scan: with every array pointer but status and num_leafs_aocl NULL only the totals
+ * (and those two when present) are written; otherwise all arrays are present with their capacities, and
+ * NHIP_ERR_ARG if one is too small. */
+typedef struct {
+    uint8_t *status;          /* n_jobs: NHIP_MS_* */
+    uint64_t *num_leafs_aocl; /* n_jobs, or NULL: the estimated AOCL leaf count, 0 for a failed job */
+    uint64_t *entry_off;      /* records + 1 */
+    uint64_t *chunk_index;    /* entries_cap */
+    uint64_t *path_off;       /* entries_cap + 1, in digests */
+    uint64_t *path;           /* path_cap digests; nhip_ms_unpack_plan leaves it alone (it may be NULL there) */
+    uint64_t *rel_off;        /* entries_cap + 1, in u32 */
+    uint32_t *rel;            /* rel_cap: the unpacked relative indices */
+    size_t entries_cap, path_cap, rel_cap;
+    size_t entries, path_digests, rel_words; /* out: the totals */
+} nhip_ms_unpacked;
+/* The codec side (no context, host only, hashes nothing): statuses and the unpacked shape without `path`. */
+int nhip_ms_unpack_plan(const uint64_t *rec_off, size_t n_jobs, const uint64_t *minimum, const uint32_t *distances,
+                        const nhip_ms_chunks *packed, nhip_ms_unpacked *out);
+/* try_unpack: the plan's output plus `path`, computed on the device (one Tip5::hash per distinct chunk, one
+ * hash_pair per completed family). */
+int nhip_ms_unpack_batch(nhip_ctx *ctx, const uint64_t *rec_off, size_t n_jobs, const uint64_t *minimum,
+                         const uint32_t *distances, const nhip_ms_chunks *packed, nhip_ms_unpacked *out);
+/* Rules 2.a-2.e in one call: nhip_ms_apply_batch with in->chunks read as packed.  A job that fails 2.a gets
+ * verdict 0, its unpack status, bad_record = UINT64_MAX and zero accumulator counts; the others run exactly as in
+ * nhip_ms_apply_batch.  The unpacked paths are produced on the device and never cross to the host. */
+int nhip_ms_apply_batch_packed(nhip_ctx *ctx, const nhip_ms_apply_in *in, nhip_ms_apply_out *out);
 
 /* ---- kernel timing (HIP events on the ctx stream around every kernel launch) ------------ */
 int nhip_timing_enable(nhip_ctx *ctx, int on);

@@ -70,7 +70,9 @@ extern "C" {
 // 2600: batched mutator-set updates (nhip_ms_apply_in, nhip_ms_apply_out, nhip_ms_apply_batch, four NHIP_MS_*)
 // 2700: block digests and the header chain (nhip_blk_header, nhip_difficulty_target, nhip_difficulty_control,
 // nhip_chain_params, NHIP_LINK_*, nhip_blk_digests, nhip_blk_chain_check)
-int nhip_abi_version(void) { return 2700; }
+// 2800: packed removal records, block rule 2.a (nhip_ms_unpack_plan, nhip_ms_unpack_batch,
+// nhip_ms_apply_batch_packed; NHIP_MS_UNPACK_*)
+int nhip_abi_version(void) { return 2800; }
 
 int nhip_set_fs_form(int form) { return nhip::set_fs_form(form) == 0 ? NHIP_OK : NHIP_ERR_ARG; }
 int nhip_set_climb_from_ops(int64_t ops) { return nhip::set_climb_from_ops(ops) == 0 ? NHIP_OK : NHIP_ERR_ARG; }

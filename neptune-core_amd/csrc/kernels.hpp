@@ -7,6 +7,7 @@
 
 #include "ab_env.hpp"
 #include "ms_shape.hpp"
+#include "ms_unpack_plan.hpp"
 #include "proof_codec.hpp"
 #include "stark.hpp"
 #include "xfe.hpp"
@@ -92,6 +93,19 @@ struct MsApplyDev {
 hipError_t launch_ms_chunk_auth_jobs(const MsApplyDev& a, size_t entries, hipStream_t st);
 hipError_t launch_ms_records_jobs(const MsApplyDev& a, size_t n_records, hipStream_t st);
 hipError_t launch_ms_apply(const MsApplyDev& a, size_t n_jobs, hipStream_t st);
+
+// ---- packed removal records (ms_unpack_kernels.hip); every pointer a device pointer
+// The program of MsUnpackPlan (ms_unpack_plan.hpp) and the buffers it runs over.
+struct MsUnpackDev {
+    const MsUnpackJob* jobs;
+    const uint32_t *leaf_slot, *leaf_cnt, *copy_slot, *op, *gath_src;
+    const uint64_t *leaf_words, *copy_src, *lvl;
+    const uint64_t* path_in;  // the packed input's structures, canonical digests
+    const uint32_t* rel_in;   // ... and its packed chunk words
+    uint64_t* arena;          // n_slots canonical digests
+    uint64_t* path_out;       // the unpacked paths
+};
+hipError_t launch_ms_unpack(const MsUnpackDev& u, size_t n_jobs, hipStream_t st);
 
 // ---- batched STARK verifier (stark_kernels.hip)
 static constexpr uint32_t AIR_LDS_HEADER = (16 + 4 + 4 + 4) * 24 + 16;  // red (per wave), zinv, derived, misc, flag

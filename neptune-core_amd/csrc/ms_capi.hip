@@ -15,16 +15,131 @@ using nhip::Stage;
 
 namespace {
 
-// The flattened chunk dictionaries of n records (counts from ms_chunks_ok), in the order every call stages them
+// The flattened chunk dictionaries of n records (counts from ms_chunks_ok), in the order every call stages them.
+// With path_dev the paths are not uploaded: *path_dev is room for them, filled on the device.
 void stage_chunks(Stage& st, const nhip_ms_chunks& ch, size_t n, const nhip::MsChunkCounts& cc, nhip::MsRecordsDev& r,
-                  const uint64_t*& path_off, const uint64_t*& path) {
+                  const uint64_t*& path_off, const uint64_t*& path, uint64_t** path_dev = nullptr) {
     const size_t E = (size_t)cc.entries;
     st.in(r.entry_off, ch.entry_off, n ? n + 1 : 0);
     st.in(r.chunk_index, ch.chunk_index, E);
     st.in(path_off, ch.path_off, n ? E + 1 : 0);
-    st.in(path, ch.path, (size_t)cc.path_digests, 5);
+    if (path_dev) st.tmp(*path_dev, (size_t)cc.path_digests, 5);
+    else st.in(path, ch.path, (size_t)cc.path_digests, 5);
     st.in(r.rel_off, ch.rel_off, n ? E + 1 : 0);
     st.in(r.rel, ch.rel, (size_t)cc.rel_words);
+}
+
+// The device program of a host plan (ms_unpack_plan.hpp) as the calls stage it: the u32 and the u64 arrays in one
+// pool each, so that a call spends six buffers on it (arena included)
+struct UnpackProgram {
+    const nhip::MsUnpackPlan& p;
+    std::vector<uint32_t> w32;
+    std::vector<uint64_t> w64;
+    const uint32_t* d32 = nullptr;
+    const uint64_t* d64 = nullptr;
+    explicit UnpackProgram(const nhip::MsUnpackPlan& plan) : p(plan) {
+        for (const std::vector<uint32_t>* v : {&p.leaf_slot, &p.leaf_cnt, &p.copy_slot, &p.op, &p.gath_src})
+            w32.insert(w32.end(), v->begin(), v->end());
+        for (const std::vector<uint64_t>* v : {&p.leaf_words, &p.copy_src, &p.lvl}) w64.insert(w64.end(), v->begin(), v->end());
+    }
+    // packed: the input's dictionaries (counts from ms_chunks_ok)
+    void declare(Stage& st, nhip::MsUnpackDev& u, const nhip_ms_chunks& packed, const nhip::MsChunkCounts& cc) {
+        st.in(u.jobs, p.jobs.data(), p.jobs.size());
+        st.in(d32, w32.data(), w32.size());
+        st.in(d64, w64.data(), w64.size());
+        st.in(u.path_in, packed.path, (size_t)cc.path_digests, 5);
+        st.in(u.rel_in, packed.rel, (size_t)cc.rel_words);
+        st.tmp(u.arena, (size_t)p.n_slots, 5);
+    }
+    // after commit()
+    void bind(nhip::MsUnpackDev& u, uint64_t* path_out) const {
+        u.leaf_slot = d32;
+        u.leaf_cnt = u.leaf_slot + p.leaf_slot.size();
+        u.copy_slot = u.leaf_cnt + p.leaf_cnt.size();
+        u.op = u.copy_slot + p.copy_slot.size();
+        u.gath_src = u.op + p.op.size();
+        u.leaf_words = d64;
+        u.copy_src = u.leaf_words + p.leaf_words.size();
+        u.lvl = u.copy_src + p.copy_src.size();
+        u.path_out = path_out;
+    }
+};
+
+// nhip_ms_apply_batch's body (in and out passed ms_apply_ok, n_jobs != 0).  With `packed`, in->chunks is the plan's
+// unpacked shape without paths, and the paths are filled on the device from the packed dictionaries first.
+int apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out, const nhip::MsApplyCounts& cnt,
+                const nhip::MsUnpackPlan* plan, const nhip_ms_chunks* packed, const nhip::MsChunkCounts* packed_counts) {
+    const size_t n = in->n_jobs;
+    const size_t R = (size_t)cnt.records, E = (size_t)cnt.chunks.entries;
+    nhip::MsApplyOrder o;
+    nhip::ms_apply_order(in, out, cnt, &o);
+    const nhip_ms_chunks none{};  // no record: the dictionaries may be absent
+    static const nhip::MsUnpackPlan no_plan;
+    UnpackProgram prog(plan ? *plan : no_plan);
+    Stage st(c);
+    nhip::MsApplyDev a{};  // rec.aocl_member null: the records as can_remove decides them
+    nhip::MsUnpackDev u{};
+    uint64_t* d_path = nullptr;
+    a.has_expected = in->msa_expected ? 1 : 0;
+    st.in(a.jobs, o.jobs.data(), n);
+    st.in(a.peaks, o.peaks.data(), o.peaks.size());
+    st.in(a.active, o.active.data(), o.active.size());
+    st.in(a.additions, in->additions, (size_t)cnt.additions, 5);
+    st.in(a.rec.minimum, in->minimum, R, 2);
+    st.in(a.rec.distances, in->distances, R, 45);
+    stage_chunks(st, R ? *in->chunks : none, R, cnt.chunks, a.rec, a.path_off, a.path, plan ? &d_path : nullptr);
+    if (plan) prog.declare(st, u, R ? *packed : none, *packed_counts);
+    st.in(a.rec_job, o.rec_job.data(), R);
+    st.in(a.entry_rec, o.entry_rec.data(), E);
+    st.in(a.idx_perm, o.idx_perm.data(), R, 45);
+    st.in(a.grp, o.grp.data(), o.grp.size());
+    st.in(a.rec_perm, o.rec_perm.data(), R);
+    st.in(a.exp_active, o.exp_active.data(), o.exp_active.size());
+    st.tmp(a.rec.auth, E);
+    st.tmp(a.rec.valid, R, 3);  // per record: valid, verdict, status
+    st.tmp(a.index_set, R, 45);
+    st.tmp(a.dig, (size_t)o.dig_total, 5);
+    st.tmp(a.aux, (size_t)o.grp_total, 2);
+    st.tmp(a.verdict, n, 2);  // per job: verdict, status
+    st.tmp(a.bad, n);
+    st.tmp(a.out_peaks, 2 * n, 64 * 5);  // AOCL, SWBF
+    st.tmp(a.out_np, n, 2);
+    st.tmp(a.out_n, n, 3);  // aocl.num_leafs, swbf_inactive.num_leafs, n_active
+    st.tmp(a.out_active, (size_t)o.win_total);
+    if (st.commit()) return st.finish();
+    a.rec.verdict = a.rec.valid + R;
+    a.rec.status = a.rec.valid + 2 * R;
+    a.status = a.verdict + n;
+    if (plan) {
+        a.path = d_path;
+        prog.bind(u, d_path);
+        st.launch([&] { return nhip::launch_ms_unpack(u, n, c->stream); });
+    }
+    st.launch([&] { return nhip::launch_ms_chunk_auth_jobs(a, E, c->stream); });
+    st.launch([&] { return nhip::launch_ms_records_jobs(a, R, c->stream); });
+    st.launch([&] { return nhip::launch_ms_apply(a, n, c->stream); });
+    // into temporaries first: the outputs stay untouched unless the whole call succeeds
+    std::vector<uint8_t> vs(2 * n);
+    std::vector<uint64_t> bad(n);
+    st.out(vs.data(), a.verdict, 2 * n);
+    st.out(bad.data(), a.bad, n);
+    if (cnt.accumulators) {
+        st.out(out->aocl_peaks, a.out_peaks, n * 64 * 5);
+        st.out(out->swbf_peaks, a.out_peaks, n * 64 * 5, n * 64 * 5);
+        st.out(out->aocl_n_peaks, a.out_np, n);
+        st.out(out->swbf_n_peaks, a.out_np, n, n);
+        st.out(out->aocl_num_leafs, a.out_n, n);
+        st.out(out->swbf_num_leafs, a.out_n, n, n);
+        st.out(out->n_active, a.out_n, n, 2 * n);
+        st.out(out->active, a.out_active, (size_t)o.win_total);
+    }
+    const int rc = st.finish();
+    if (rc == NHIP_OK) {
+        std::copy(vs.begin(), vs.begin() + n, out->verdict);
+        std::copy(vs.begin() + n, vs.end(), out->status);
+        std::copy(bad.begin(), bad.end(), out->bad_record);
+    }
+    return rc;
 }
 
 }  // namespace
@@ -175,69 +290,81 @@ int nhip_ms_verify_batch(nhip_ctx* c, const nhip_msa* msa, const uint64_t* items
 int nhip_ms_apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out) {
     nhip::MsApplyCounts cnt;
     if (!c || nhip::ms_apply_ok(in, out, &cnt)) return NHIP_ERR_ARG;
+    if (in->n_jobs == 0) return NHIP_OK;
+    try {
+        return apply_batch(c, in, out, cnt, nullptr, nullptr, nullptr);
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// RemovalRecordList::try_unpack for n_jobs packed lists: the host plan decides every status and
+// lays out the unpacked shape (ms_unpack_plan.cpp); k_ms_unpack computes the path digests.
+int nhip_ms_unpack_batch(nhip_ctx* c, const uint64_t* rec_off, size_t n_jobs, const uint64_t* minimum,
+                         const uint32_t* distances, const nhip_ms_chunks* packed, nhip_ms_unpacked* out) {
+    if (!c || !out) return NHIP_ERR_ARG;
+    const nhip::MsPackedIn in{rec_off, n_jobs, minimum, distances, packed};
+    nhip::MsUnpackCounts cnt;
+    if (nhip::ms_packed_ok(in, &cnt)) return NHIP_ERR_ARG;
+    try {
+        nhip::MsUnpackPlan plan;
+        int rc = nhip::ms_unpack_plan(in, cnt, &plan);
+        if (rc != NHIP_OK) return rc;
+        const bool count_pass = nhip::ms_unpacked_is_count_pass(out);
+        if ((rc = nhip::ms_unpacked_write(plan, n_jobs, true, out)) != NHIP_OK) return rc;
+        const size_t PD = plan.gath_src.size();
+        if (count_pass || PD == 0) return NHIP_OK;
+        UnpackProgram prog(plan);
+        Stage st(c);
+        nhip::MsUnpackDev u{};
+        uint64_t* d_path;
+        prog.declare(st, u, *packed, cnt.chunks);
+        st.tmp(d_path, PD, 5);
+        if (st.commit()) return st.finish();
+        prog.bind(u, d_path);
+        st.launch([&] { return nhip::launch_ms_unpack(u, n_jobs, c->stream); });
+        st.out(out->path, d_path, 5 * PD);
+        return st.finish();
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// Block::validate rules 2.a-2.e: nhip_ms_apply_batch over the plan's unpacked shape, its paths filled on the device
+// by k_ms_unpack ahead of the three launches; the jobs that fail 2.a are overwritten with their unpack status.
+int nhip_ms_apply_batch_packed(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out) {
+    nhip::MsApplyCounts cnt;
+    if (!c || nhip::ms_apply_ok(in, out, &cnt)) return NHIP_ERR_ARG;
     const size_t n = in->n_jobs;
     if (n == 0) return NHIP_OK;
     try {
-        const size_t R = (size_t)cnt.records, E = (size_t)cnt.chunks.entries;
-        nhip::MsApplyOrder o;
-        nhip::ms_apply_order(in, out, cnt, &o);
-        const nhip_ms_chunks none{};  // no record: the dictionaries may be absent
-        Stage st(c);
-        nhip::MsApplyDev a{};  // rec.aocl_member null: the records as can_remove decides them
-        a.has_expected = in->msa_expected ? 1 : 0;
-        st.in(a.jobs, o.jobs.data(), n);
-        st.in(a.peaks, o.peaks.data(), o.peaks.size());
-        st.in(a.active, o.active.data(), o.active.size());
-        st.in(a.additions, in->additions, (size_t)cnt.additions, 5);
-        st.in(a.rec.minimum, in->minimum, R, 2);
-        st.in(a.rec.distances, in->distances, R, 45);
-        stage_chunks(st, R ? *in->chunks : none, R, cnt.chunks, a.rec, a.path_off, a.path);
-        st.in(a.rec_job, o.rec_job.data(), R);
-        st.in(a.entry_rec, o.entry_rec.data(), E);
-        st.in(a.idx_perm, o.idx_perm.data(), R, 45);
-        st.in(a.grp, o.grp.data(), o.grp.size());
-        st.in(a.rec_perm, o.rec_perm.data(), R);
-        st.in(a.exp_active, o.exp_active.data(), o.exp_active.size());
-        st.tmp(a.rec.auth, E);
-        st.tmp(a.rec.valid, R, 3);  // per record: valid, verdict, status
-        st.tmp(a.index_set, R, 45);
-        st.tmp(a.dig, (size_t)o.dig_total, 5);
-        st.tmp(a.aux, (size_t)o.grp_total, 2);
-        st.tmp(a.verdict, n, 2);  // per job: verdict, status
-        st.tmp(a.bad, n);
-        st.tmp(a.out_peaks, 2 * n, 64 * 5);  // AOCL, SWBF
-        st.tmp(a.out_np, n, 2);
-        st.tmp(a.out_n, n, 3);  // aocl.num_leafs, swbf_inactive.num_leafs, n_active
-        st.tmp(a.out_active, (size_t)o.win_total);
-        if (st.commit()) return st.finish();
-        a.rec.verdict = a.rec.valid + R;
-        a.rec.status = a.rec.valid + 2 * R;
-        a.status = a.verdict + n;
-        st.launch([&] { return nhip::launch_ms_chunk_auth_jobs(a, E, c->stream); });
-        st.launch([&] { return nhip::launch_ms_records_jobs(a, R, c->stream); });
-        st.launch([&] { return nhip::launch_ms_apply(a, n, c->stream); });
-        // into temporaries first: the outputs stay untouched unless the whole call succeeds
-        std::vector<uint8_t> vs(2 * n);
-        std::vector<uint64_t> bad(n);
-        st.out(vs.data(), a.verdict, 2 * n);
-        st.out(bad.data(), a.bad, n);
-        if (cnt.accumulators) {
-            st.out(out->aocl_peaks, a.out_peaks, n * 64 * 5);
-            st.out(out->swbf_peaks, a.out_peaks, n * 64 * 5, n * 64 * 5);
-            st.out(out->aocl_n_peaks, a.out_np, n);
-            st.out(out->swbf_n_peaks, a.out_np, n, n);
-            st.out(out->aocl_num_leafs, a.out_n, n);
-            st.out(out->swbf_num_leafs, a.out_n, n, n);
-            st.out(out->n_active, a.out_n, n, 2 * n);
-            st.out(out->active, a.out_active, (size_t)o.win_total);
+        const nhip::MsPackedIn pin{in->rec_off, n, in->minimum, in->distances, in->chunks};
+        nhip::MsUnpackCounts pc;
+        if (nhip::ms_packed_ok(pin, &pc)) return NHIP_ERR_ARG;
+        nhip::MsUnpackPlan plan;
+        int rc = nhip::ms_unpack_plan(pin, pc, &plan);
+        if (rc != NHIP_OK) return rc;
+        const nhip_ms_chunks unpacked{plan.entry_off.data(), plan.chunk_index.data(), plan.path_off.data(), nullptr,
+                                      plan.rel_off.data(),   plan.rel.data()};
+        nhip_ms_apply_in in2 = *in;
+        in2.chunks = &unpacked;
+        nhip::MsApplyCounts cnt2 = cnt;
+        cnt2.chunks.entries = plan.chunk_index.size();
+        cnt2.chunks.path_digests = plan.gath_src.size();
+        cnt2.chunks.rel_words = plan.rel.size();
+        rc = apply_batch(c, &in2, out, cnt2, &plan, in->chunks, &pc.chunks);
+        if (rc != NHIP_OK) return rc;
+        for (size_t j = 0; j < n; ++j) {
+            if (plan.status[j] == NHIP_MS_OK) continue;
+            out->verdict[j] = 0;
+            out->status[j] = plan.status[j];
+            out->bad_record[j] = UINT64_MAX;
+            if (cnt.accumulators) {
+                out->aocl_n_peaks[j] = out->swbf_n_peaks[j] = 0;
+                out->aocl_num_leafs[j] = out->swbf_num_leafs[j] = out->n_active[j] = 0;
+            }
         }
-        const int rc = st.finish();
-        if (rc == NHIP_OK) {
-            std::copy(vs.begin(), vs.begin() + n, out->verdict);
-            std::copy(vs.begin() + n, vs.end(), out->status);
-            std::copy(bad.begin(), bad.end(), out->bad_record);
-        }
-        return rc;
+        return NHIP_OK;
     } catch (const std::bad_alloc&) {
         return NHIP_ERR_OOM;
     }

@@ -158,6 +158,15 @@ class MsApplyOut(ctypes.Structure):
                 ("active_off", ctypes.c_void_p), ("active", ctypes.c_void_p), ("n_active", ctypes.c_void_p)]
 
 
+class MsUnpacked(ctypes.Structure):
+    """nhip_ms_unpacked: statuses and the unpacked dictionaries of nhip_ms_unpack_plan / nhip_ms_unpack_batch."""
+    _fields_ = [("status", ctypes.c_void_p), ("num_leafs_aocl", ctypes.c_void_p), ("entry_off", ctypes.c_void_p),
+                ("chunk_index", ctypes.c_void_p), ("path_off", ctypes.c_void_p), ("path", ctypes.c_void_p),
+                ("rel_off", ctypes.c_void_p), ("rel", ctypes.c_void_p), ("entries_cap", ctypes.c_size_t),
+                ("path_cap", ctypes.c_size_t), ("rel_cap", ctypes.c_size_t), ("entries", ctypes.c_size_t),
+                ("path_digests", ctypes.c_size_t), ("rel_words", ctypes.c_size_t)]
+
+
 _pp = ctypes.POINTER(ctypes.c_void_p)
 
 # (name, argtypes) for every symbol of include/neptune_hip.h
@@ -236,6 +245,10 @@ SIGNATURES = {
     "nhip_ms_verify_batch": ([_vp, ctypes.POINTER(Msa), _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(MsChunks), _sz,
                               _vp, _vp], ctypes.c_int),
     "nhip_ms_apply_batch": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut)], ctypes.c_int),
+    "nhip_ms_unpack_plan": ([_vp, _sz, _vp, _vp, ctypes.POINTER(MsChunks), ctypes.POINTER(MsUnpacked)], ctypes.c_int),
+    "nhip_ms_unpack_batch": ([_vp, _vp, _sz, _vp, _vp, ctypes.POINTER(MsChunks), ctypes.POINTER(MsUnpacked)],
+                             ctypes.c_int),
+    "nhip_ms_apply_batch_packed": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut)], ctypes.c_int),
     "nhip_proof_decodes": ([_vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof)],
                            ctypes.c_int),
     "nhip_verify_batch": ([_vp, _vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof),

@@ -252,6 +252,17 @@ def mutator_set_update_valid(ctx, msa_before, removal_records, addition_records,
     return verdict, status
 
 
+def mutator_set_update_valid_packed(ctx, msa_before, packed_inputs, addition_records, msa_claimed) -> Tuple[bool, int]:
+    """`Block::validate` rules 2.a-2.e (mod.rs:811-849) in one GPU call: `packed_inputs` is the block body's
+    `transaction_kernel.inputs` as the block carries them (`RemovalRecordList::pack`); they are unpacked on the
+    device (2.a) into the buffers `mutator_set_update_valid`'s kernels read.  Returns `(ok, status)`; a list that
+    does not unpack gives `(False, UNPACK_*)`."""
+    from .mutator_set import MutatorSetUpdate, apply_update_batch_packed
+    update = MutatorSetUpdate(list(packed_inputs), list(addition_records))
+    verdict, status, _, _ = apply_update_batch_packed(ctx, [(msa_before, update)], [msa_claimed])[0]
+    return verdict, status
+
+
 def accumulator_after(ctx, msa, guesser_fee_addition_records):
     """`Block::mutator_set_accumulator_after` (mod.rs:369-378): `msa` with the guesser-fee addition records
     applied, an update with additions only.  Raises when `msa` is inconsistent."""

@@ -14,6 +14,11 @@ consensus step after "the proof verifies", batched.
   (mod.rs:369-378) for many independent `(msa_before, MutatorSetUpdate)` jobs: the accumulator after
   each update, computed on the device.
 
+* `unpack_removal_records_batch(ctx, jobs)` — `RemovalRecordList::try_unpack`
+  (removal_record/removal_record_list.rs:653-658), block rule 2.a, for many packed lists; `unpack_plan_batch(jobs)`
+  is its host half (statuses and shapes, no GPU), and `apply_update_batch_packed(ctx, jobs, expected=None)` is
+  rules 2.a-2.e in one call over packed lists.
+
 The types mirror the reference's over numpy; every verdict is the device's.  Where the reference
 would panic or truncate (an index past the active window, or >= 2^76) the record is rejected with
 `OUT_OF_RANGE`.
@@ -34,8 +39,20 @@ CHUNK_SIZE = 1 << 12
 BATCH_SIZE = 1 << 3
 OK, ABSENT_CHUNK, BAD_MMR_PATH, ALREADY_REMOVED, OUT_OF_RANGE, NOT_IN_AOCL = range(6)
 INCONSISTENT, DUPLICATE_RECORD, UPDATE_IMPOSSIBLE, UPDATE_MISMATCH = range(6, 10)  # apply_update_batch only
+# rule 2.a (unpack_removal_records_batch, apply_update_batch_packed): try_unpack's errors, then "the reference panics"
+UNPACK_PAYLOAD_TOO_BIG, UNPACK_INCONSISTENT_LENGTH, UNPACK_NONZERO_TRAILING_PADDING, UNPACK_ILLEGAL_TREE_HEIGHT, \
+    UNPACK_DUPLICATE_TREE_HEIGHTS, UNPACK_INDEX_TOO_BIG, UNPACK_INCONSISTENT_CHUNKS, UNPACK_STRUCTURE_COUNT, \
+    UNPACK_STRUCTURE_LENGTH, UNPACK_PANIC = range(10, 20)
 STATUS_NAMES = ("OK", "ABSENT_CHUNK", "BAD_MMR_PATH", "ALREADY_REMOVED", "OUT_OF_RANGE", "NOT_IN_AOCL",
                 "INCONSISTENT", "DUPLICATE_RECORD", "UPDATE_IMPOSSIBLE", "UPDATE_MISMATCH")
+UNPACK_STATUS_NAMES = ("UNPACK_PAYLOAD_TOO_BIG", "UNPACK_INCONSISTENT_LENGTH", "UNPACK_NONZERO_TRAILING_PADDING",
+                       "UNPACK_ILLEGAL_TREE_HEIGHT", "UNPACK_DUPLICATE_TREE_HEIGHTS", "UNPACK_INDEX_TOO_BIG",
+                       "UNPACK_INCONSISTENT_CHUNKS", "UNPACK_STRUCTURE_COUNT", "UNPACK_STRUCTURE_LENGTH", "UNPACK_PANIC")
+
+
+def status_name(status: int) -> str:
+    """The name of any NHIP_MS_* status, the rule 2.a ones included."""
+    return (STATUS_NAMES + UNPACK_STATUS_NAMES)[status]
 
 
 def _digests(x, n=None) -> np.ndarray:
@@ -279,11 +296,13 @@ class PackedApply:
                                   self.expected)
         self.cout = _lib.MsApplyOut(*(a[f].ctypes.data for f, _ in _lib.MsApplyOut._fields_))
 
-    def call(self, ctx) -> int:
-        return ctx.lib.nhip_ms_apply_batch(ctx.handle, ctypes.byref(self.cin), ctypes.byref(self.cout))
+    def call(self, ctx, packed=False) -> int:
+        """`packed`: the removals are packed lists (`nhip_ms_apply_batch_packed`)."""
+        fn = ctx.lib.nhip_ms_apply_batch_packed if packed else ctx.lib.nhip_ms_apply_batch
+        return fn(ctx.handle, ctypes.byref(self.cin), ctypes.byref(self.cout))
 
 
-def apply_update_batch(ctx, jobs, expected=None):
+def apply_update_batch(ctx, jobs, expected=None, _packed=False):
     """`jobs`: `(MutatorSetAccumulator before, MutatorSetUpdate)` pairs, independent of each other;
     `expected`: one `MutatorSetAccumulator` per job, or None.  Per job `(verdict, status, bad_record,
     msa_after)`: `bad_record` is the position in the job's removals of the record the status blames
@@ -293,7 +312,7 @@ def apply_update_batch(ctx, jobs, expected=None):
     if n == 0:
         return []
     pa = PackedApply(jobs, expected)
-    check(pa.call(ctx), "nhip_ms_apply_batch")
+    check(pa.call(ctx, _packed), "nhip_ms_apply_batch_packed" if _packed else "nhip_ms_apply_batch")
     a = pa.arrays
     out = []
     for j in range(n):
@@ -306,4 +325,70 @@ def apply_update_batch(ctx, jobs, expected=None):
             after = MutatorSetAccumulator(mmrs[0], mmrs[1], [int(x) for x in a["active"][lo:lo + int(a["n_active"][j])]])
         bad = int(a["bad_record"][j])
         out.append((bool(a["verdict"][j]), status, None if bad == 2 ** 64 - 1 else bad, after))
+    return out
+
+
+def apply_update_batch_packed(ctx, jobs, expected=None):
+    """`apply_update_batch` over jobs whose `removals` are packed lists (`RemovalRecordList::pack`): block rules
+    2.a-2.e in one call.  A job whose list does not unpack has verdict False, its `UNPACK_*` status, no blamed
+    record and no accumulator.  The unpacked paths are produced and consumed on the device."""
+    return apply_update_batch(ctx, jobs, expected, _packed=True)
+
+
+class PackedLists:
+    """The arguments of `nhip_ms_unpack_plan` / `nhip_ms_unpack_batch` for `jobs`, each a packed list of
+    `RemovalRecord`s (an entry's key in the place of its chunk index, its authentication structure in the place of
+    its path, its chunk's packed words as the relative indices)."""
+
+    def __init__(self, jobs):
+        self.n = len(jobs)
+        records = [r for job in jobs for r in job]
+        self.n_records = len(records)
+        self.rec_off = _csr([len(job) for job in jobs])
+        self.minimum, self.distances = _index_arrays(records)
+        self.index_sets = [r.absolute_indices for r in records]
+        self.packed = pack_chunks(records)
+        self.chunks = self.packed._c()
+
+    def run(self, lib, handle=None):
+        """Both calls of the two-call pattern.  `(status, num_leafs_aocl, PackedChunks)`; with no `handle` the host
+        plan alone, whose `path` stays zero."""
+        n = self.n
+        status, leafs = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint64)
+        out = _lib.MsUnpacked(status=_ptr(status), num_leafs_aocl=_ptr(leafs))
+        args = (self.rec_off.ctypes.data, n, _ptr(self.minimum), _ptr(self.distances), ctypes.byref(self.chunks),
+                ctypes.byref(out))
+        name = "nhip_ms_unpack_plan" if handle is None else "nhip_ms_unpack_batch"
+        call = (lambda: lib.nhip_ms_unpack_plan(*args)) if handle is None else \
+            (lambda: lib.nhip_ms_unpack_batch(handle, *args))
+        check(call(), name)
+        E, PD, W = int(out.entries), int(out.path_digests), int(out.rel_words)
+        u = PackedChunks(np.zeros(self.n_records + 1, dtype=np.uint64), np.zeros(E, dtype=np.uint64),
+                         np.zeros(E + 1, dtype=np.uint64), np.zeros((PD, 5), dtype=np.uint64),
+                         np.zeros(E + 1, dtype=np.uint64), np.zeros(W, dtype=np.uint32))
+        out.entry_off, out.chunk_index, out.path_off = u.entry_off.ctypes.data, _ptr(u.chunk_index), u.path_off.ctypes.data
+        out.path, out.rel_off, out.rel = _ptr(u.path), u.rel_off.ctypes.data, _ptr(u.rel)
+        out.entries_cap, out.path_cap, out.rel_cap = E, PD, W
+        check(call(), name)
+        return status, leafs, u
+
+
+def unpack_plan_batch(jobs):
+    """The host half of `unpack_removal_records_batch` (no GPU): `(status, num_leafs_aocl, PackedChunks)` over all
+    records of all jobs, the paths' digests left zero."""
+    return PackedLists(jobs).run(_lib.load())
+
+
+def unpack_removal_records_batch(ctx, jobs):
+    """`RemovalRecordList::try_unpack` of every packed list in `jobs`: per job `(status, records)`, the records
+    None unless the status is OK.  Every status is the host plan's integer decision; every path digest is the
+    device's."""
+    pl = PackedLists(jobs)
+    status, _, u = pl.run(ctx.lib, ctx.handle)
+    dictionaries = unpack_chunks(u)
+    out = []
+    for j in range(pl.n):
+        lo, hi = int(pl.rec_off[j]), int(pl.rec_off[j + 1])
+        recs = [RemovalRecord(pl.index_sets[r], dictionaries[r]) for r in range(lo, hi)]
+        out.append((int(status[j]), recs if int(status[j]) == OK else None))
     return out

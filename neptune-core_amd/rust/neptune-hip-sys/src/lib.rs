@@ -257,6 +257,37 @@ pub const NHIP_MS_INCONSISTENT: u8 = 6;
 pub const NHIP_MS_DUPLICATE_RECORD: u8 = 7;
 pub const NHIP_MS_UPDATE_IMPOSSIBLE: u8 = 8;
 pub const NHIP_MS_UPDATE_MISMATCH: u8 = 9;
+pub const NHIP_MS_UNPACK_PAYLOAD_TOO_BIG: u8 = 10;
+pub const NHIP_MS_UNPACK_INCONSISTENT_LENGTH: u8 = 11;
+pub const NHIP_MS_UNPACK_NONZERO_TRAILING_PADDING: u8 = 12;
+pub const NHIP_MS_UNPACK_ILLEGAL_TREE_HEIGHT: u8 = 13;
+pub const NHIP_MS_UNPACK_DUPLICATE_TREE_HEIGHTS: u8 = 14;
+pub const NHIP_MS_UNPACK_INDEX_TOO_BIG: u8 = 15;
+pub const NHIP_MS_UNPACK_INCONSISTENT_CHUNKS: u8 = 16;
+pub const NHIP_MS_UNPACK_STRUCTURE_COUNT: u8 = 17;
+pub const NHIP_MS_UNPACK_STRUCTURE_LENGTH: u8 = 18;
+pub const NHIP_MS_UNPACK_PANIC: u8 = 19;
+
+/// Statuses and the unpacked dictionaries of `nhip_ms_unpack_plan` / `nhip_ms_unpack_batch` (two-call sizing:
+/// every array pointer but `status` and `num_leafs_aocl` null writes the totals only).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_ms_unpacked {
+    pub status: *mut u8,
+    pub num_leafs_aocl: *mut u64,
+    pub entry_off: *mut u64,
+    pub chunk_index: *mut u64,
+    pub path_off: *mut u64,
+    pub path: *mut u64,
+    pub rel_off: *mut u64,
+    pub rel: *mut u32,
+    pub entries_cap: usize,
+    pub path_cap: usize,
+    pub rel_cap: usize,
+    pub entries: usize,
+    pub path_digests: usize,
+    pub rel_words: usize,
+}
 
 /// The jobs of one `nhip_ms_apply_batch` call (CSR over the jobs; `msa_expected` may be null).
 #[repr(C)]
@@ -493,6 +524,13 @@ extern "C" {
                                 status: *mut u8) -> c_int;
     pub fn nhip_ms_apply_batch(ctx: *mut nhip_ctx, input: *const nhip_ms_apply_in,
                                out: *mut nhip_ms_apply_out) -> c_int;
+    pub fn nhip_ms_unpack_plan(rec_off: *const u64, n_jobs: usize, minimum: *const u64, distances: *const u32,
+                               packed: *const nhip_ms_chunks, out: *mut nhip_ms_unpacked) -> c_int;
+    pub fn nhip_ms_unpack_batch(ctx: *mut nhip_ctx, rec_off: *const u64, n_jobs: usize, minimum: *const u64,
+                                distances: *const u32, packed: *const nhip_ms_chunks,
+                                out: *mut nhip_ms_unpacked) -> c_int;
+    pub fn nhip_ms_apply_batch_packed(ctx: *mut nhip_ctx, input: *const nhip_ms_apply_in,
+                                      out: *mut nhip_ms_apply_out) -> c_int;
     pub fn nhip_timing_enable(ctx: *mut nhip_ctx, on: c_int) -> c_int;
     pub fn nhip_timing_read(ctx: *mut nhip_ctx, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
 }
