@@ -520,6 +520,133 @@ def test_hardfork_height_picks_the_rule_set(ctx, chain):
         assert [g_[1] for g_ in got[1:]] == want
 
 
+# ================================================================== 130 blocks: three workgroups, non-trivial integers
+BIG_N = 130                                   # k_block_links / k_block_masts: workgroups of 64, 64 and 2 lanes
+MAXIMUM = (1 << 160) - 1
+MMR_MERGES = (1, 2, 5, 31, 63)                # leaf counts 2^k - 1: k merges, no peak kept
+
+
+def _limbs(v, n):
+    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(n)]
+
+
+def _synthetic_parent(g, **header):
+    """A parent no rule is checked on: a consistent block MMR (5 leaves, 2 peaks), a timestamp near T0, a height
+    that is not genesis; `header` overrides."""
+    b = _random_block(g, B.SINGLE_PROOF, [g.randrange(P) for _ in range(g.randrange(13))])
+    b["header"].update(height=1000 + g.randrange(1000), timestamp=T0 + g.randrange(1_000_000))
+    b["header"].update(header)
+    b["body"]["block_mmr_accumulator"] = {"leaf_count": 5, "peaks": [B._rd(g), B._rd(g)]}
+    return b
+
+
+def _big_pairs(seed=2705):
+    """130 synthetic blocks for one call (no proof of work is solved): accepted pairs with multi-limb integers, one
+    mutant per pair that fails exactly the rule in question, and children of parents with difficulties 1, 2, 3 and 7
+    whose digest decides mock proof of work.  Returns (pairs, order in the buffer, accepted, mutants, mock)."""
+    T.use_c_backend()
+    g = random.Random(seed)
+    p = _params(allows_mock_pow=True)
+    pairs, accepted, mutants, mock = Pairs(), [], {}, []
+
+    def accept(parent, dt, name, mutate, status, mutant_parent=None):
+        k = pairs.add(parent, -1, "parent: " + name)
+        child = _child_of(g, parent, p, dt, n_proof=g.randrange(13))
+        accepted.append(pairs.add(child, k, name))
+        if mutant_parent is not None:            # the rule reads the parent: a pair of its own
+            k = pairs.add(mutant_parent, -1, "mutant parent: " + name)
+            bad = _child_of(g, mutant_parent, p, dt, n_proof=g.randrange(13))
+        else:
+            bad = copy.deepcopy(child)
+            mutate(bad)
+        mutants[pairs.add(bad, k, "mutant: " + name)] = status
+
+    def flip_difficulty(c):
+        c["header"]["difficulty"][3] ^= 1
+
+    def flip_pow(c):
+        c["header"]["cumulative_proof_of_work"][5] ^= 1
+
+    def flip_peak(c):
+        pk = c["body"]["block_mmr_accumulator"]["peaks"]
+        pk[-1] = [(pk[-1][0] + 1) % P] + list(pk[-1][1:])
+
+    # multi-limb difficulties: unchanged at the target interval, raised to the MAXIMUM overflow, lowered
+    for dv, dt in ((1 << 32, 100), ((1 << 95) + 12345, 700), (MAXIMUM, 40)):
+        accept(_synthetic_parent(g, difficulty=_limbs(dv, 5)), dt, f"difficulty {dv:#x}", flip_difficulty, R.DIFFICULTY)
+    # cumulative proof of work that carries through every limb and wraps
+    accept(_synthetic_parent(g, cumulative_proof_of_work=[0xFFFFFFFF] * 6, difficulty=[6000, 0, 0, 0, 0]), 100,
+           "pow carries through six limbs", flip_pow, R.CUMULATIVE_POW)
+    # the child's timestamp wraps past p: p - 1 + 100 = 99, and p - 1 + minimum_block_time = 0 <= 99.  One
+    # millisecond earlier the parent's p - 2 + 1 = p - 1 does not wrap and is above the child's 98.
+    accept(_synthetic_parent(g, timestamp=P - 1), 100, "timestamp wraps past p", None, R.MINIMUM_BLOCK_TIME,
+           mutant_parent=_synthetic_parent(g, timestamp=P - 2))
+    # height p - 1, whose child has height 0
+    accept(_synthetic_parent(g, height=P - 1), 100, "height p - 1", lambda c: c["header"].update(height=1), R.BLOCK_HEIGHT)
+    # block MMRs: 2^k - 1 leaves (k merges, no peak kept) and 2^40 leaves (no merge)
+    for k in MMR_MERGES:
+        parent = _synthetic_parent(g)
+        parent["body"]["block_mmr_accumulator"] = {"leaf_count": (1 << k) - 1, "peaks": [B._rd(g) for _ in range(k)]}
+        accept(parent, 100, f"mmr with 2^{k} - 1 leaves", flip_peak, R.BLOCK_MMR_UPDATE)
+    parent = _synthetic_parent(g)
+    parent["body"]["block_mmr_accumulator"] = {"leaf_count": 1 << 40, "peaks": [B._rd(g)]}
+    accept(parent, 100, "mmr with 2^40 leaves", flip_peak, R.BLOCK_MMR_UPDATE)
+    # mock proof of work: Difficulty::target does not clamp, so the targets are (p^5 - 1) / 1, 2, 3 and 7
+    roots = [pairs.add(_synthetic_parent(g, difficulty=[d, 0, 0, 0, 0]), -1, f"parent: difficulty {d}") for d in (1, 2, 3, 7)]
+    while len(pairs.blocks) < BIG_N:
+        k = roots[len(mock) % 4]
+        mock.append(pairs.add(_child_of(g, pairs.blocks[k], p, 100, n_proof=g.randrange(13)), k, "mock pow child"))
+    # the buffer's order: shuffled, then a mock parent and an accepted child in the last workgroup's two lanes
+    order = list(range(BIG_N))
+    g.shuffle(order)
+    for pos, blk in ((128, roots[1]), (129, accepted[0])):
+        at = order.index(blk)
+        order[at], order[pos] = order[pos], order[at]
+    return pairs, order, accepted, mutants, mock, p
+
+
+@pytest.fixture(scope="module")
+def big():
+    pairs, order, accepted, mutants, mock, p = _big_pairs()
+    want = pairs.expected(p)
+    hashes = [R.block_hash(b) for b in pairs.blocks]
+    # all on the reference: the shape of the call and both mock verdicts
+    assert len(pairs.blocks) == BIG_N and len(mock) >= 40
+    pos = {b: k for k, b in enumerate(order)}
+    wg = [(pos[i] // 64, pos[par] // 64) for i, par in enumerate(pairs.parent_of) if par >= 0]
+    assert sum(c < q for c, q in wg) >= 5 and sum(c > q for c, q in wg) >= 5        # parent_of across workgroups
+    assert any(c == 2 for c, _ in wg) and any(q == 2 and c != 2 for c, q in wg)     # and into / out of the last one
+    assert all(want[i] == (R.OK, False) for i in accepted)                          # targets far below any digest
+    assert all(want[i][0] == s for i, s in mutants.items())
+    verdicts = []
+    for i in mock:
+        target = R.difficulty_target(pairs.blocks[pairs.parent_of[i]]["header"]["difficulty"])
+        verdicts.append(W.digest_le(hashes[i], target))
+        assert want[i] == (R.OK, verdicts[-1])
+    assert verdicts.count(True) >= 5 and verdicts.count(False) >= 5
+    return pairs, order, p, want, hashes
+
+
+def test_130_blocks_links_and_mock_pow_over_three_workgroups(ctx, big):
+    """One nhip_blk_chain_check call: every status and pow_ok is the reference's, the accepted pairs with multi-limb
+    difficulties, a wrapping cumulative pow, a wrapping timestamp, height p - 1 and block MMRs of up to 63 merges, their
+    mutants, and mock proof of work against targets of difficulties 1, 2, 3 and 7."""
+    pairs, order, p, want, _ = big
+    got = pairs.run(ctx, p, order)
+    for i, name in enumerate(pairs.names):
+        assert got[i] == want[i], (i, name)
+
+
+def test_130_block_digests_over_three_workgroups(ctx, big):
+    from neptune_hip import blocks as NB
+    pairs, order, _, _, hashes = big
+    data = b"".join(B.encode_block(pairs.blocks[i]) for i in order)
+    dig = NB.block_digests(ctx, data, _records(data), H)
+    assert len(dig) == BIG_N
+    for k, i in enumerate(order):
+        assert _dig(dig[k]) == hashes[i], (k, pairs.names[i])
+
+
 # ================================================================== errors
 def test_argument_errors(ctx, chain):
     import neptune_hip._lib as L
