@@ -10,7 +10,7 @@
  * unchanged, so this table must equal the crate's enum.  PARITY UNPINNED: no vector under
  * /root/reference fixes these indices; the order below is the public triton-air 1.0 enum.
  *
- * One list, used by the kernels (stark_kernels.hip), the host (stark_host.cpp: descriptor check)
+ * One list, used by the kernels (stark_kernels.hip), the host (air_host.cpp: descriptor check)
  * and the C oracle (oracle/stark_oracle.c); the Python oracle (oracle/stark_ref.py CHALLENGE_IDS)
  * keeps an independent copy that tests/test_challenge_ids.py compares with this file.
  *

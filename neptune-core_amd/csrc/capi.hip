@@ -378,7 +378,7 @@ int nhip_mtree_verify(nhip_ctx* c, const uint64_t* roots, size_t n_roots, const 
 }
 
 // ------------------------------------------------------------------ wire bytes -> words
-int nhip_internal_is_pinned(const void* p, size_t bytes);  // stark_host.cpp
+int nhip_internal_is_pinned(const void* p, size_t bytes);  // host_pinned.cpp
 
 // The device counterpart of nhip_le_words: the spans' raw bytes uploaded run by run (wire.hpp), gathered
 // by k_wire_words into one aligned word buffer (span i at the sum of the lengths before it), read back.

@@ -18,7 +18,7 @@
 using nhip::hip_fail;
 using nhip::Stage;
 
-extern "C" int nhip_internal_is_pinned(const void* p, size_t bytes);  // stark_host.cpp
+extern "C" int nhip_internal_is_pinned(const void* p, size_t bytes);  // host_pinned.cpp
 extern "C" void* nhip_internal_staging(nhip_ctx* c, size_t bytes);    // capi.hip
 namespace nhip {  // bincode.cpp: one walk of a block each
 int blk_header_append(const uint8_t* bytes, size_t n_bytes, uint32_t pow_tree_height, uint64_t offset,

@@ -1,4 +1,4 @@
-// Batched STARK verification: descriptors shared by the host decoder (stark_host.cpp) and the
+// Batched STARK verification: descriptors shared by the host code (stark_host.cpp, air_host.cpp) and the
 // phase kernels (stark_kernels.hip).
 //
 // Restates the structure of `triton_vm::verify(Stark::default(), &claim, &proof)` (triton-vm
@@ -108,7 +108,7 @@ struct AirNode {
     uint64_t k0, k1, k2;  // AIR_CONST value (raw Montgomery)
 };
 
-// The AIR compiled for k_ood_air (nhip_air_create, stark_host.cpp air_compile): steps of independent
+// The AIR compiled for k_ood_air (nhip_air_create, air_host.cpp air_compile): steps of independent
 // instructions whose results live in reusable slots (liveness-allocated: a slot is reused from the
 // step after its value's last use), constants in a global table, OOD-row inputs loaded once into
 // slots, and every constraint value copied (ACC) into its own slot among the top C, which the kernel

@@ -2,7 +2,7 @@
 Cargo.lock:4194, ~600 constraints, tens of thousands of circuit nodes after degree lowering):
 the synthetic AIR with 620 constraints, bloated to ~22k nodes by identically-zero terms
 (stark_ref.bloat_air: same constraint values, real evaluation work).  Its compiled program (the
-liveness-priority schedule of stark_host.cpp air_compile) keeps every value in LDS; the same circuit
+liveness-priority schedule of air_host.cpp air_compile) keeps every value in LDS; the same circuit
 with the LDS part capped (nhip_air_create_ex's lds_slots) runs k_ood_air's global-memory slot
 overflow.  An accepting proof and mutated ones give the oracle's verdicts either way, and the
 Fiat-Shamir transcript is the oracle's."""

@@ -1,4 +1,4 @@
-"""The per-kind layout of the compiled OOD program (stark_host.cpp air_compile, nhip_air_program and
+"""The per-kind layout of the compiled OOD program (air_host.cpp air_compile, nhip_air_program and
 nhip_air_segments) on the host, no GPU.  k_ood_air runs a step as three loops, one per segment (the
 copies, the products, the sums and differences), each from its thread 0, and picks the operation by
 the segment, so the bounds must partition every step and every instruction must be of its segment's

@@ -1,4 +1,4 @@
-"""The OOD program compiler (stark_host.cpp air_compile, nhip_air_program) on the host, no GPU: the
+"""The OOD program compiler (air_host.cpp air_compile, nhip_air_program) on the host, no GPU: the
 step schedule is a valid parallel program and computes every constraint.  Within one step the
 instructions run concurrently on k_ood_air's threads, so a step may not read a slot another
 instruction of the same step writes, nor write a slot twice; values come from earlier steps only.
