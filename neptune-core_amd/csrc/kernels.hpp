@@ -116,41 +116,11 @@ static constexpr uint32_t AIR_LDS_SLOTS_MAX = (AIR_LDS_BUDGET - AIR_LDS_HEADER) 
 // live in MP_SHARDS shards (shard = proof index % MP_SHARDS) so the per-level slot reservations of
 // the plan workgroups spread over MP_SHARDS counters instead of contending on one.
 static constexpr uint32_t MP_SHARDS = 16;
-// levels with at most this many hash ops run the 16-lane-row Tip5 (latency-bound regime)
-static constexpr uint64_t MP_WIDE_MAX_OPS = 48 * 1024;
-// the last levels whose ops (multiproof + last-codeword parents) all fit this many rows are climbed
-// by one workgroup in one launch (k_mp_hash_tail), up to MP_TAIL_LEVELS_MAX levels
-#ifndef NHIP_MP_TAIL_MAX_OPS
-#define NHIP_MP_TAIL_MAX_OPS 256
-#endif
-static constexpr uint64_t MP_TAIL_MAX_OPS = NHIP_MP_TAIL_MAX_OPS;
+// k_mp_hash_tail climbs at most this many levels (TailCaps); which kernel instance runs at which batch
+// size and level, and every threshold of that choice: stark_launch_plan.hpp
 static constexpr uint32_t MP_TAIL_LEVELS_MAX = 32;
-// batches of at most this many proofs climb every tree in its own workgroup (k_mp_climb), one
-// launch for all levels, instead of one launch per level
-static constexpr uint32_t MP_CLIMB_MAX_PROOFS = 32;
-inline uint32_t climb_max_proofs() {  // NHIP_CLIMB_MAX overrides (A/B runs)
-    static const uint32_t v = [] {
-        const char* e = nhip::ab_env("NHIP_CLIMB_MAX");
-        return e ? (uint32_t)std::strtoul(e, nullptr, 10) : MP_CLIMB_MAX_PROOFS;
-    }();
-    return v;
-}
-// batches below this many proofs replay Fiat-Shamir on the two-row pair Tip5 (k_fs_replay_wide):
-// one-collection latency 1.89 -> 1.65 ms, while from 512 proofs on (several steps in flight) the
-// one-row form is 2-3% faster (profiles/r01i/ab_pair.log)
-static constexpr uint32_t FS_PAIR_MAX_PROOFS = 512;
-// batches of at least this many proofs replay Fiat-Shamir on the quad Tip5 (k_fs_replay_quad);
-// NHIP_FS_QUAD_MIN overrides (A/B runs).  0.61x the row form's VALU instructions (profiles/r03g
-// PMC), but fewer, longer replay waves: with 256-thread workgroups (one replay wave per SIMD of the
-// CUs they land on) 4,096 proofs +1.5% and 2,048 +1.6% over the row form, 1,024 -3%; 64-thread
-// workgroups -7 to -9% at every size, 512 / 1,024 threads -1 to -25% (profiles/r03g, 2 repetitions)
-static constexpr uint32_t FS_QUAD_MIN_PROOFS = 2048;
-static constexpr uint32_t FS_QUAD_WG = 256;  // k_fs_replay_quad workgroup size
-// batches below this many proofs hash their Merkle levels with the 7-wave k_mp_hash instance, larger
-// ones with the 6-wave one; NHIP_MP_SMALL_MAX overrides (A/B runs).  7 waves: 2,048 proofs +1.3%,
-// 1,024 +1.2%, 512 +3%; 4,096 -0.6% (profiles/r03ze, r03zf)
-static constexpr uint32_t MP_SMALL_MAX_PROOFS = 4096;
-static constexpr uint32_t OOD_WIDE_MAX_PROOFS = 64;  // k_ood_air<1024> up to this many proofs per batch
+// k_roots_verdicts_small's one workgroup: the root checks and the verdicts of n_records + n_proofs <= this
+static constexpr uint32_t ROOTS_ONE_WG = 1024;
 struct MpRoot {
     uint64_t code;  // source code of the tree's final node, ~0 = no check (skipped or already failed)
     uint64_t root_off;
@@ -232,18 +202,48 @@ struct StarkBatchDev {
     Xfe* air_gslots;               // [n_proofs][air_gslot_n]
 };
 
-// events: 0 start (after k_decode, aux stream) | fs | rows | mp plan | mp hash levels | mp roots | ood | fri | deep | 9 verdicts
-// 10: main stream at the aux-chain release point, 11: aux stream after that wait, 12: before k_decode,
-// 13: before FRI on the main stream (small batches)
-static constexpr int STARK_EVENTS = 14;
+// The events of a batch launch: the phase timestamps and the cross-stream fork / join points
+// (stark_launch_plan.hpp has the cross-stream set and the pair that brackets each reported phase).
+enum StarkEvent : int {
+    EV_DECODED = 0,       // aux stream, after k_decode
+    EV_FS_DONE = 1,       // aux, after the Fiat-Shamir replay
+    EV_ROWS_DONE = 2,     // main, after the row hashing
+    EV_PLAN_DONE = 3,     // aux, after the Merkle plan
+    EV_HASH_DONE = 4,     // main, after the last Merkle hash launch
+    EV_ROOTS_DONE = 5,    // main, after the root checks
+    EV_OOD_DONE = 6,      // aux, after k_ood_air
+    EV_FRI_DONE = 7,      // after k_fri: aux, or main for small batches
+    EV_DEEP_DONE = 8,     // aux, after k_deep_rows8: the main stream joins here
+    EV_VERDICTS = 9,      // main, after the verdicts
+    EV_AUX_RELEASE = 10,  // main, at the point the OOD / FRI / DEEP chain is released
+    EV_AUX_START = 11,    // aux, after waiting for that release
+    EV_FORK = 12,         // main, before k_decode: the aux stream starts here
+    EV_FRI_START = 13,    // before FRI of a small batch (main; aux when fused with the plan)
+    STARK_EVENTS
+};
+// The pair of events that brackets each phase nhip_stats reports.  Phases overlap (two streams):
+// each is timed from the event its inputs wait on.  These are the spans of a batch that runs FRI on
+// the aux stream; plan_launch (stark_launch_plan.hpp) sets the others.
+struct PhaseSpan {
+    StarkEvent from, to;
+};
+struct PhaseBrackets {
+    PhaseSpan decode{EV_FORK, EV_DECODED}, fs{EV_DECODED, EV_FS_DONE}, rows{EV_DECODED, EV_ROWS_DONE},
+        plan{EV_FS_DONE, EV_PLAN_DONE};
+    PhaseSpan hash[2] = {{EV_ROWS_DONE, EV_HASH_DONE}, {EV_PLAN_DONE, EV_HASH_DONE}};  // the shorter of the two
+    PhaseSpan roots{EV_HASH_DONE, EV_ROOTS_DONE}, ood{EV_AUX_START, EV_OOD_DONE};
+    PhaseSpan fri{EV_OOD_DONE, EV_FRI_DONE}, deep{EV_FRI_DONE, EV_DEEP_DONE};  // FRI after OOD, DEEP after FRI
+    PhaseSpan total{EV_FORK, EV_VERDICTS};
+};
 struct StarkPhaseTimer {
     hipEvent_t ev[STARK_EVENTS];
     hipEvent_t lev[2 * MAX_HASH_LAUNCHES];  // per hash launch: dispatch begin / end (nullptr = untimed)
     hipEvent_t rev[2] = {nullptr, nullptr};  // the row-hashing launch: dispatch begin / end (nullptr = untimed)
     bool launch_events = false;  // use lev / rev on this launch (nhip_batch_set_launch_timing)
     bool phase_marks = true;     // record the phase events (off in a captured graph: no phase split)
+    // written by each enqueue (launch_stark_phases)
     uint32_t mp_hash_launches;
-    uint32_t aux_after_level = 0;  // hash levels launched before the OOD/FRI/DEEP chain is released
+    PhaseBrackets spans;  // the events that bracket each phase of this launch
 };
 
 // Phases on two streams: st_aux runs the latency-bound chain (Fiat-Shamir -> Merkle plan -> OOD ->

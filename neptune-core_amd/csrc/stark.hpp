@@ -7,17 +7,23 @@
 // all proofs of a call (phase-synchronous design, SURVEY.md §7 "hard parts" 4):
 //   k_decode        : BFieldCodec proof stream -> ProofDesc (offsets into the batch word buffer)
 //                     and the proof's Fiat-Shamir program, one wave per proof (proof_codec.hpp)
-//   k_fs_replay_wide: Fiat-Shamir sponge replay, one 16-lane DPP row (two below 512 proofs) per
-//                     proof (challenges, weights, z, FRI folding challenges, indices)
-//   k_hash_rows     : Tip5::hash_varlen of every revealed main / aux / quotient row
-//   k_mp_plan, k_mp_hash*, k_mp_roots : Merkle authentication structures (main, aux, quotient,
-//                     FRI rounds): index-only plan per (proof, tree group), then one launch per
-//                     tree level over all trees of all proofs, then the root compares
+//   k_fs_replay_wide / _quad : Fiat-Shamir sponge replay per proof (challenges, weights, z, FRI
+//                     folding challenges, indices) on two 16-lane DPP rows, one row, or four lanes
+//   k_hash_rows / _wide : Tip5::hash_varlen of every revealed main / aux / quotient row
+//   k_mp_plan, k_mp_hash / _wide / _tail, k_mp_climb, k_mp_roots : Merkle authentication structures
+//                     (main, aux, quotient, FRI rounds): index-only plan per (proof, tree group),
+//                     then the tree levels (one launch per level over all trees of all proofs, the
+//                     small top levels in one, or every tree climbed by its own workgroup), then
+//                     the root compares
 //   k_ood_air       : AIR circuit at the out-of-domain point, zerofiers, quotient identity; one
-//                     workgroup per proof, circuit levels evaluated in LDS
+//                     workgroup per proof, the circuit a slot program evaluated in LDS
 //   k_fri           : collinearity folds, last codeword root / agreement / low degree
-//   k_deep          : DEEP recombination at the revealed rows vs the first FRI codeword
-// Every check ORs a bit into the proof's fail word; verdict = (fail == 0).
+//   k_deep_rows8    : DEEP recombination at the revealed rows vs the first FRI codeword
+//   k_verdicts      : verdict = (fail == 0); every check ORs a bit into the proof's fail word
+//   k_fs_rows_small, k_plan_fri_small, k_roots_verdicts_small : two of the above in one launch,
+//                     for small one-stream batches
+// Which form and instance runs at which batch size and tree level, and in which order on the two
+// streams: stark_launch_plan.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

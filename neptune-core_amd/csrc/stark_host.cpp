@@ -38,10 +38,6 @@ using namespace nhip;
 
 namespace {
 
-// hash levels launched before the OOD / FRI / DEEP chain is released (NHIP_AUX_AFTER_LEVEL
-// overrides); tuned on MI355X
-constexpr uint32_t AUX_AFTER_LEVEL_DEFAULT = 0;
-
 // A batch's proofs given as spans of a wire buffer (the in-place feed path) instead of nhip_proof records.
 struct WireSrc {
     const uint8_t* bytes;
@@ -577,8 +573,6 @@ int launch_resources(nhip_batch* b) {
     if (!b->timed) {
         const char* pm = nhip::ab_env("NHIP_PHASE_MARKS");  // A/B: 0 = the phase events off
         b->tm.phase_marks = !(pm && pm[0] == '0');
-        const char* al = nhip::ab_env("NHIP_AUX_AFTER_LEVEL");
-        b->tm.aux_after_level = al ? (uint32_t)std::strtoul(al, nullptr, 10) : AUX_AFTER_LEVEL_DEFAULT;
         if (!r.made) {
             for (int i = 0; i < STARK_EVENTS; ++i)
                 if (hipEventCreate(&r.ev[i]) != hipSuccess) return NHIP_ERR_HIP;
@@ -844,26 +838,26 @@ int nhip_batch_wait(nhip_ctx* ctx, nhip_batch* b, uint8_t* verdicts, uint8_t* al
     b->H.perms_static = cnt[CNT_PERMS_STATIC];
     b->H.perms_lcw = cnt[CNT_PERMS_LCW];
     b->merkle_perms = reserved - cnt[CNT_MP_SKIPPED] + b->H.perms_lcw;
-    // phases overlap (two streams): each is timed from the event its inputs wait on
-    auto el = [&](int a, int c) {
+    // each phase between the events the launch's plan brackets it with
+    auto el = [&](PhaseSpan s) {
         float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, b->tm.ev[a], b->tm.ev[c]);
+        (void)hipEventElapsedTime(&ms, b->tm.ev[s.from], b->tm.ev[s.to]);
         return (double)ms;
     };
     if (b->last_graph || !b->tm.phase_marks) {
         b->ph = {};  // a replayed launch (its events are the graph's own, untimed) or one without marks
     } else if (n) {
-        b->ph.decode = el(12, 0);
-        b->ph.fs = el(0, 1);
-        b->ph.rows = el(0, 2);
-        b->ph.plan = el(1, 3);
-        b->ph.hash = std::min(el(2, 4), el(3, 4));
-        b->ph.roots = el(4, 5);
-        b->ph.ood = el(11, 6);
-        const bool small = n <= climb_max_proofs();  // FRI on the main stream (launch_stark_phases)
-        b->ph.fri = small ? el(13, 7) : el(6, 7);
-        b->ph.deep = small ? el(6, 8) : el(7, 8);
-        b->ph.total = el(12, 9);
+        const PhaseBrackets& sp = b->tm.spans;
+        b->ph.decode = el(sp.decode);
+        b->ph.fs = el(sp.fs);
+        b->ph.rows = el(sp.rows);
+        b->ph.plan = el(sp.plan);
+        b->ph.hash = std::min(el(sp.hash[0]), el(sp.hash[1]));
+        b->ph.roots = el(sp.roots);
+        b->ph.ood = el(sp.ood);
+        b->ph.fri = el(sp.fri);
+        b->ph.deep = el(sp.deep);
+        b->ph.total = el(sp.total);
     }
     const uint8_t* v = h_out + b->rb.verdicts_off;
     if (verdicts && n) std::memcpy(verdicts, v, n);

@@ -15,6 +15,7 @@
 #include "kernels.hpp"
 #include "proof_codec.hpp"
 #include "stark.hpp"
+#include "stark_launch_plan.hpp"
 #include "tip5_device.hpp"
 #include "xfe.hpp"
 
@@ -31,19 +32,12 @@ namespace nhip {
 __device__ __forceinline__ void latency_priority() {
     if constexpr (NHIP_LAT_PRIO > 0) __builtin_amdgcn_s_setprio(NHIP_LAT_PRIO);
 }
-// Oldest-first wave priority: the AGE_PRIO_OLDEST oldest batch launches in flight on the device run
-// their row hashing and Merkle levels one priority level above their kernel's base (the sponge
-// replay keeps its own), so the in-flight steps drift apart (the oldest finishes first) instead of
-// moving through their phases in lockstep.  Measured
-// (profiles/r05z/ab/age_prio_ab_r05w.txt, 3 alternating repetitions per run): config 4 in the
-// driver's 20 steps at 4,096 proofs +1.4%, 2,048 +0.9%, 1,024 and 512 equal, so from
-// AGE_PRIO_MIN_PROOFS on.  Raising the sponge replay too (NHIP_AGE_PRIO_FS=1): 512 -1 to -2% (round 5);
-// 4,096 +0.6% and 2,048 equal, within the run-to-run spread (round 6, once the quad launch took
-// age_sponge: round 5's 4,096 arms were the same code; profiles/r06/ab_age_prio_fs.txt), so it stays off.  g_batches_done counts the
-// device's finished batch launches (k_verdicts); a launch's seq is its place in the device's launch
-// order.
-static constexpr uint32_t AGE_PRIO_OLDEST = 2;
-static constexpr uint32_t AGE_PRIO_MIN_PROOFS = 2048;
+// Oldest-first wave priority: the oldest batch launches in flight on the device run their row
+// hashing and Merkle levels one priority level above their kernel's base (the sponge replay keeps
+// its own), so the in-flight steps drift apart (the oldest finishes first) instead of moving through
+// their phases in lockstep.  How many launches count as oldest, from which batch
+// size, and the measurements: stark_launch_plan.hpp.  g_batches_done counts the device's finished
+// batch launches (k_verdicts); a launch's seq is its place in the device's launch order.
 __device__ uint32_t g_batches_done;
 struct AgePrio {
     uint32_t seq, k;
@@ -781,7 +775,7 @@ __device__ __forceinline__ void lcw_node(const uint64_t* __restrict__ words, con
 // 6 waves per SIMD (<= 80 VGPRs): with hash_pair's MDS finished two outputs at a time
 // (NHIP_PAIR_MDS_GROUP) the kernel needs 77 VGPRs and no scratch (5 waves and a 20-byte spill before,
 // 109 VGPRs unconstrained).  Config 4 +1.1-1.4% at 4,096 proofs, +2.3-3.4% at 512 (profiles/r03x).
-// Batches below MP_SMALL_MAX_PROOFS (kernels.hpp) launch the 7-wave instance (72 VGPRs, a 24-byte
+// Small batches (stark_launch_plan.hpp has the bound) launch the 7-wave instance (72 VGPRs, a 24-byte
 // spill): 512 to 2,048 proofs +1.2-4.3%, 4,096 proofs -0.6% (profiles/r03ze, r03zf).
 #ifndef NHIP_MP_WAVES
 #define NHIP_MP_WAVES 6
@@ -1204,7 +1198,7 @@ __device__ Xfe eval_terminal_wave(uint32_t n, Xfe c, Sym sym) {
 // with sum_k z^k * segment_k(z^4).  Also stores the OOD linear combinations used by DEEP:
 // [sum w*curr row, sum w*next row, sum w*segs].
 // BLOCK = 256 for batches that fill the GPU (the hashing needs the wave slots); 1,024 for small ones
-// (OOD_WIDE_MAX_PROOFS), where one proof's evaluation is on the critical path and the CUs are idle.
+// (stark_launch_plan.hpp has the bound), where one proof's evaluation is on the critical path and the CUs are idle.
 #ifndef NHIP_OOD_WAVES
 #define NHIP_OOD_WAVES 1
 #endif
@@ -1740,7 +1734,6 @@ __global__ void k_verdicts(const uint32_t* __restrict__ fail, uint32_t n, uint8_
 // Small batches (n_records + n_proofs <= ROOTS_ONE_WG): the root checks and the verdicts in one
 // workgroup, one launch (one dependent packet fewer).  The fail words are read back past the L1 (a
 // root check's atomicOr lands in L2) after every lane's atomics have completed (fence + barrier).
-static constexpr uint32_t ROOTS_ONE_WG = 1024;
 template <bool MW>
 __global__ void __launch_bounds__(ROOTS_ONE_WG) k_roots_verdicts_small(
     const uint64_t* __restrict__ words, const ProofDesc* __restrict__ desc, const uint64_t* __restrict__ dig,
@@ -1755,9 +1748,14 @@ __global__ void __launch_bounds__(ROOTS_ONE_WG) k_roots_verdicts_small(
 }
 
 // ------------------------------------------------------------------ launchers
+// What a batch launches (which kernel instance, grid, order, events) is decided by plan_launch
+// (stark_launch_plan.hpp); launch_phases below only enqueues that plan.
+
 // A launch with dispatch begin / end events when given (hipExtLaunchKernel: the launch-timing
 // passes), a plain launch otherwise, so an untimed batch's launch sequence can be captured into a
-// HIP graph (nhip_batch_launch).
+// HIP graph (nhip_batch_launch).  The events take the dispatch's own begin / end timestamps (what
+// the rocprofv3 kernel trace reports): the launch's duration without the dispatch gap before it,
+// which a plain event pair around back-to-back launches would also hold.
 template <typename K, typename... A>
 static void launch_ev(K kernel, dim3 grid, dim3 block, size_t shm, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
                       A... args) {
@@ -1765,25 +1763,8 @@ static void launch_ev(K kernel, dim3 grid, dim3 block, size_t shm, hipStream_t s
     else hipLaunchKernelGGL(kernel, grid, block, shm, s, args...);
 }
 
-// OOD evaluator workgroup: 1,024 threads for batches of at most OOD_WIDE_MAX_PROOFS proofs
-// (NHIP_OOD_WIDE_MAX overrides, A/B runs), else 256
-static bool ood_wide(uint32_t n) {
-    static const uint32_t lim = [] {
-        const char* v = nhip::ab_env("NHIP_OOD_WIDE_MAX");
-        return v ? (uint32_t)std::strtoul(v, nullptr, 10) : OOD_WIDE_MAX_PROOFS;
-    }();
-    return n <= lim;
-}
-
-// Level-synchronous batches of deep trees (>= CLIMB_FROM_MIN_LEVELS hash levels: BASELINE config 5's
-// height-23 proofs have 26) hand the rest of their trees to one per-tree climb launch (k_mp_climb
-// from a start level) at the first level with at most climb_from_ops() hash ops: the top levels of a
-// deep tree are launch-bound, not VALU-bound.  Measured (profiles/r05z/ab/climb_from_ab_r05q.txt):
-// config 5's 64 proofs +3-6% at 4,096 ops; config 4's trees (<= 19 levels) are not affected (at
-// 4,096 ops without the depth gate: 512 proofs -2 to -4%, 4,096 equal; 16K / 64K ops: worse).
-// nhip_set_climb_from_ops sets the threshold for every depth (tests: 0 = never).
-static constexpr uint32_t CLIMB_FROM_MIN_LEVELS = 24;
-static constexpr uint64_t CLIMB_FROM_OPS_DEFAULT = 4096;
+// The forced climb-from threshold and Fiat-Shamir form (tests and A/B runs); plan_launch takes the
+// current values.
 static std::atomic<int64_t>& climb_from_forced() {
     static std::atomic<int64_t> v(-1);
     return v;
@@ -1793,45 +1774,8 @@ int set_climb_from_ops(int64_t ops) {
     climb_from_forced().store(ops, std::memory_order_relaxed);
     return 0;
 }
-static uint64_t climb_from_ops(uint32_t hash_levels) {
-    const int64_t v = climb_from_forced().load(std::memory_order_relaxed);
-    if (v >= 0) return (uint64_t)v;
-    return hash_levels >= CLIMB_FROM_MIN_LEVELS ? CLIMB_FROM_OPS_DEFAULT : 0ull;
-}
-
-
-// batches of at most this many proofs hash their revealed rows in the 16-lane form (k_hash_rows_wide)
-static constexpr uint32_t ROWS_WIDE_MAX_PROOFS = 32;
-static uint32_t rows_wide_max() {
-    static const uint32_t v = [] {
-        const char* e = nhip::ab_env("NHIP_ROWS_WIDE_MAX");
-        return e ? (uint32_t)std::strtoul(e, nullptr, 10) : ROWS_WIDE_MAX_PROOFS;
-    }();
-    return v;
-}
-
-// Fiat-Shamir replay form for an n-proof batch (see k_fs_replay_wide / k_fs_replay_quad):
-// 0 = 16-lane row, 1 = two-row pair, 2 = quad.  A forced form (nhip_set_fs_form: tests and A/B
-// runs; NHIP_FS_FORM=row|pair|quad sets the initial value, read once) overrides the size rule.
-enum FsForm { FS_ROW = 0, FS_PAIR = 1, FS_QUAD = 2 };
-// k_fs_replay_quad workgroup size (NHIP_QUAD_WG = 64..1024 overrides, A/B runs)
-static uint32_t quad_wg() {
-    static const uint32_t v = [] {
-        const char* e = nhip::ab_env("NHIP_QUAD_WG");
-        const uint32_t w = e ? (uint32_t)std::strtoul(e, nullptr, 10) : FS_QUAD_WG;
-        return (w >= 64 && w <= 1024 && w % 64 == 0) ? w : FS_QUAD_WG;
-    }();
-    return v;
-}
 static std::atomic<int>& fs_form_forced() {
-    static std::atomic<int> f([] {
-        if (const char* v = nhip::ab_env("NHIP_FS_FORM")) {
-            if (v[0] == 'q') return (int)FS_QUAD;
-            if (v[0] == 'p') return (int)FS_PAIR;
-            if (v[0] == 'r') return (int)FS_ROW;
-        }
-        return -1;
-    }());
+    static std::atomic<int> f(launch_knobs().fs_form_init);
     return f;
 }
 int set_fs_form(int form) {
@@ -1839,286 +1783,205 @@ int set_fs_form(int form) {
     fs_form_forced().store(form, std::memory_order_relaxed);
     return 0;
 }
-static FsForm fs_form(uint32_t n) {
-    static const uint32_t quad_min = [] {
-        const char* v = nhip::ab_env("NHIP_FS_QUAD_MIN");
-        return v ? (uint32_t)std::strtoul(v, nullptr, 10) : FS_QUAD_MIN_PROOFS;
-    }();
-    const int forced = fs_form_forced().load(std::memory_order_relaxed);
-    if (forced >= 0) return (FsForm)forced;
-    if (n < FS_PAIR_MAX_PROOFS) return FS_PAIR;
-    return n >= quad_min ? FS_QUAD : FS_ROW;
-}
 
 #ifdef NHIP_AB_BUILD
-// A/B build only: an empty kernel, NHIP_PAD_PACKETS of them after each kernel of the batch (what one
+// A/B build only: an empty kernel, LaunchKnobs::pad_packets of them after each kernel of the batch (what one
 // more dependent packet in a batch's chain costs under load)
 __global__ void k_pad_packet() {}
 #endif
 
+// The batch's two-stream timeline: sa runs the latency-bound chain, st the VALU-bound hashing.
 template <bool MW>
 static hipError_t launch_phases(const StarkBatchDev& b, hipStream_t st, hipStream_t sa, StarkPhaseTimer* tm) {
     const uint32_t n = b.n_proofs;
     if (n == 0) return hipSuccess;
     (void)hipGetLastError();  // the launch errors below are this launch's, not an earlier call's
-    const uint32_t k = b.dims.num_checks;
-    const uint32_t tpp = 4 + b.max_R;
-    // Events: the phase timestamps (every one, when tm->phase_marks) and the cross-stream fork / join
-    // points (SYNC: recorded whenever the batch runs on two streams).  A replayed graph of a
-    // one-stream batch (no phase split, nhip_batch_set_graph) records none and waits on none: each
-    // record or wait is one more packet in the batch's dependent chain.
-    const bool two = st != sa;
-    constexpr uint32_t SYNC = (1u << 12) | (1u << 0) | (1u << 1) | (1u << 3) | (1u << 7) | (1u << 10) | (1u << 8);
-    auto mark = [&](int i, hipStream_t s) {
-        if (tm->phase_marks || (two && ((SYNC >> i) & 1u))) (void)hipEventRecord(tm->ev[i], s);
+    const LaunchKnobs& kn = launch_knobs();
+    LaunchInput in{};
+    in.n = n, in.k = b.dims.num_checks, in.max_R = b.max_R;
+    in.mp_levels = b.mp.levels, in.mp_cap_host = b.mp_cap_host, in.max_lcw = b.max_lcw;
+    in.global_slots = b.air_gslot_n > 0, in.air_block = b.air_block;
+    in.two_streams = st != sa, in.phase_marks = tm->phase_marks;
+    in.launch_events = tm->launch_events, in.hash_events = tm->lev[0] != nullptr;
+    in.fs_form_forced = fs_form_forced().load(std::memory_order_relaxed);
+    in.climb_from_forced = climb_from_forced().load(std::memory_order_relaxed);
+    const LaunchPlan p = plan_launch(in, kn);
+    if (!p.ok) return hipErrorInvalidValue;
+    tm->mp_hash_launches = p.n_steps;
+    tm->spans = p.spans;
+    // Events: the phase timestamps (every one, when the batch takes phase marks) and the
+    // cross-stream fork / join points (recorded whenever the batch runs on two streams).  A replayed
+    // graph of a one-stream batch (no phase split, nhip_batch_set_graph) records none and waits on
+    // none: each record or wait is one more packet in the batch's dependent chain.
+    auto mark = [&](StarkEvent e, hipStream_t s) {
+        if (p.records(e)) (void)hipEventRecord(tm->ev[e], s);
     };
-    auto wait = [&](hipStream_t s, int i) {
-        if (two) (void)hipStreamWaitEvent(s, tm->ev[i], 0);
+    auto wait = [&](hipStream_t s, StarkEvent e) {
+        if (p.two_streams) (void)hipStreamWaitEvent(s, tm->ev[e], 0);
     };
 #ifdef NHIP_AB_BUILD
-    static const int pad_n = [] {
-        const char* e = nhip::ab_env("NHIP_PAD_PACKETS");
-        return e ? std::atoi(e) : 0;
-    }();
     auto pad = [&](hipStream_t s) {
-        for (int i = 0; i < pad_n; ++i) hipLaunchKernelGGL(k_pad_packet, dim3(1), dim3(64), 0, s);
+        for (int i = 0; i < kn.pad_packets; ++i) hipLaunchKernelGGL(k_pad_packet, dim3(1), dim3(64), 0, s);
     };
 #else
     auto pad = [](hipStream_t) {};
 #endif
-    // small batches: every Merkle tree climbed in one launch (k_mp_climb), and FRI on the main
-    // stream (it needs only the sponge samples) concurrent with the plan and OOD on the aux stream;
-    // DEEP (which needs both) waits for it.  With the climb that short, OOD -> FRI -> DEEP in a row
-    // would be the critical path.
-    const bool small = n <= climb_max_proofs();
-    // this launch's place in the device's launch order, for the oldest-first priority: the 2 oldest
-    // batches in flight one level up, for batches of at least AGE_PRIO_MIN_PROOFS (A/B knobs:
-    // NHIP_AGE_PRIO=k sets k for every size, 0 = off; NHIP_AGE_PRIO_FS=1 raises the sponge too)
-    static const int64_t age_env = [] {
-        const char* e = nhip::ab_env("NHIP_AGE_PRIO");
-        return e ? (int64_t)std::strtoul(e, nullptr, 10) : (int64_t)-1;
-    }();
-    const uint32_t age_k = age_env >= 0 ? (uint32_t)age_env : (n >= AGE_PRIO_MIN_PROOFS ? AGE_PRIO_OLDEST : 0u);
+    // this launch's place in the device's launch order, for the oldest-first priority
     static std::atomic<uint32_t> seq_ctr[64];
     int dev = 0;
     (void)hipGetDevice(&dev);
-    const AgePrio age{seq_ctr[(uint32_t)dev & 63u].fetch_add(1u, std::memory_order_relaxed), age_k};
-    static const bool age_fs = [] {  // NHIP_AGE_PRIO_FS=1 (A/B): the sponge replay raised as well
-        const char* e = nhip::ab_env("NHIP_AGE_PRIO_FS");
-        return e && e[0] == '1';
-    }();
-    const AgePrio age_sponge{age.seq, age_fs ? age.k : 0u};
+    const AgePrio age{seq_ctr[(uint32_t)dev & 63u].fetch_add(1u, std::memory_order_relaxed), p.age_k};
+    const AgePrio age_sponge{age.seq, p.age_sponge_k};
+    const uint32_t k = in.k, tpp = p.trees_per_proof;
+    const LcwTree lcw{b.lcw, b.max_lcw};
+    auto timed = [&](const HashStep& h, int end) { return h.slot < 0 ? nullptr : tm->lev[2 * h.slot + end]; };
+    auto ood = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(n), dim3(p.ood_threads), b.air_lds_bytes, sa, b.words, b.desc, n, b.dims,
+                           b.air_prog, b.air_prog_off, b.air_n_levels, b.air_consts, b.air_cons_off, b.xs, b.ood, b.fail,
+                           b.air_lds_slots, b.air_gslots, b.air_gslot_n);
+    };
+
     // fork: the aux stream starts after everything already queued on st (counter resets)
-    mark(12, st);
-    wait(sa, 12);
-    // proof-stream decode of every proof (descriptors, Fiat-Shamir programs, fail words), on the
-    // aux stream: the Fiat-Shamir replay is the next packet of that queue, so it is dispatched
-    // the moment decode ends, before the row hashing (main stream, waiting on the same event) can
-    // fill the CUs.  Decoding on the main stream instead let k_hash_rows take every wave slot first
-    // and stretched the latency-bound sponge replay 1.6 -> 5.0 ms (config 4, one step in flight).
+    mark(EV_FORK, st);
+    wait(sa, EV_FORK);
+    // ---- aux stream: the latency-bound chain.  Proof-stream decode of every proof (descriptors,
+    // Fiat-Shamir programs, fail words) runs here: the Fiat-Shamir replay is the next packet of that
+    // queue, so it is dispatched the moment decode ends, before the row hashing (main stream, waiting
+    // on the same event) can fill the CUs.  Decoding on the main stream instead let k_hash_rows take
+    // every wave slot first and stretched the latency-bound sponge replay 1.6 -> 5.0 ms (config 4,
+    // one step in flight).
     hipLaunchKernelGGL(k_decode<MW>, dim3(n), dim3(64), 0, sa, b.words, b.in, n, b.D, b.fs_stride, b.xs_stride, b.desc,
                        b.ops, b.fail, b.counters);
     pad(sa);
-    mark(0, sa);
-    wait(st, 0);
-    // ---- aux stream: latency-bound chain
-    // small batches: the sponge replay is the critical path and most SIMDs are idle, so two rows
-    // per proof (pair form) for a shorter permutation; large ones: one row per proof (fewer
-    // lane-instructions while the other steps' hashing fills the GPU); the largest: four lanes per
-    // proof (quad form, fewer lane-instructions again).  NHIP_FS_FORM forces one.
-    const FsForm ff = fs_form(n);
-    // one stream, pair form, 16-lane rows: the replay and the row hashing in one launch
-    static const bool fuse_env = [] {  // A/B build: NHIP_FUSE_SMALL=0 launches them apart
-        const char* e = nhip::ab_env("NHIP_FUSE_SMALL");
-        return !(e && e[0] == '0');
-    }();
-    const bool fused = fuse_env && !two && ff == FS_PAIR && n <= rows_wide_max() && !tm->launch_events;
-    const uint64_t rows = (uint64_t)n * k;
-    if (fused) {
-        const uint32_t fs_blocks = (n * 32 + 255) / 256;
-        const uint32_t rows_gx = (uint32_t)((rows * 16 + 255) / 256);
-        hipLaunchKernelGGL(k_fs_rows_small<MW>, dim3(fs_blocks + 3 * rows_gx), dim3(256), 0, sa, b.words, b.desc,
-                           b.ops, n, b.xs, b.idx, b.fail, age_sponge, fs_blocks, rows_gx, k, b.dims, b.dig);
-    } else if (ff == FS_PAIR)
-        hipLaunchKernelGGL((k_fs_replay_wide<true, MW>), dim3((n * 32 + 255) / 256), dim3(256), 0, sa, b.words, b.desc,
-                           b.ops, n, b.xs, b.idx, b.fail, age_sponge);
-    else if (ff == FS_QUAD)
-        hipLaunchKernelGGL(k_fs_replay_quad<MW>, dim3((n * 4 + quad_wg() - 1) / quad_wg()), dim3(quad_wg()), 0, sa, b.words, b.desc, b.ops, n,
+    mark(EV_DECODED, sa);
+    wait(st, EV_DECODED);
+    if (p.fused_fs_rows)
+        hipLaunchKernelGGL(k_fs_rows_small<MW>, dim3(p.fs_grid), dim3(p.fs_block), 0, sa, b.words, b.desc, b.ops, n, b.xs,
+                           b.idx, b.fail, age_sponge, p.fs_blocks, p.rows_gx, k, b.dims, b.dig);
+    else if (p.fs_form == FS_PAIR)
+        hipLaunchKernelGGL((k_fs_replay_wide<true, MW>), dim3(p.fs_grid), dim3(p.fs_block), 0, sa, b.words, b.desc, b.ops,
+                           n, b.xs, b.idx, b.fail, age_sponge);
+    else if (p.fs_form == FS_QUAD)
+        hipLaunchKernelGGL(k_fs_replay_quad<MW>, dim3(p.fs_grid), dim3(p.fs_block), 0, sa, b.words, b.desc, b.ops, n,
                            b.xs, b.idx, b.fail, age_sponge);
     else
-        hipLaunchKernelGGL((k_fs_replay_wide<false, MW>), dim3((n * 16 + 255) / 256), dim3(256), 0, sa, b.words, b.desc,
+        hipLaunchKernelGGL((k_fs_replay_wide<false, MW>), dim3(p.fs_grid), dim3(p.fs_block), 0, sa, b.words, b.desc,
                            b.ops, n, b.xs, b.idx, b.fail, age_sponge);
     pad(sa);
-    mark(1, sa);
-    // one stream, small, k <= 256: the plan and FRI in one launch
-    static const bool fuse2_env = [] {  // A/B build: NHIP_FUSE_PLAN_FRI=0 launches them apart
-        const char* e = nhip::ab_env("NHIP_FUSE_PLAN_FRI");
-        return !(e && e[0] == '0');
-    }();
-    const bool fused2 = fuse2_env && !two && small && k <= 256;
-    if (fused2) {
-        mark(13, sa);
-        hipLaunchKernelGGL(k_plan_fri_small<MW>, dim3(n * (1 + b.max_R) + n), dim3(256), 0, sa, b.words, b.desc, n,
-                           k, tpp, 1 + b.max_R, b.dig, b.idx, b.mp, b.fail, b.counters + CNT_MP_SKIPPED, b.dims, b.xs,
+    mark(EV_FS_DONE, sa);
+    if (p.fused_plan_fri) {
+        mark(EV_FRI_START, sa);
+        hipLaunchKernelGGL(k_plan_fri_small<MW>, dim3(n * p.plan_groups + n), dim3(256), 0, sa, b.words, b.desc, n, k,
+                           tpp, p.plan_groups, b.dig, b.idx, b.mp, b.fail, b.counters + CNT_MP_SKIPPED, b.dims, b.xs,
                            b.xdom);
-    } else if (k <= 128)
-        hipLaunchKernelGGL(k_mp_plan<128>, dim3(n, 1 + b.max_R), dim3(128), 0, sa, b.words, b.desc, n, k, tpp, b.dig,
+    } else if (p.plan_block == 128) {
+        hipLaunchKernelGGL(k_mp_plan<128>, dim3(n, p.plan_groups), dim3(128), 0, sa, b.words, b.desc, n, k, tpp, b.dig,
                            b.idx, b.mp, b.fail, b.counters + CNT_MP_SKIPPED);
-    else
-        hipLaunchKernelGGL(k_mp_plan<256>, dim3(n, 1 + b.max_R), dim3(256), 0, sa, b.words, b.desc, n, k, tpp, b.dig,
+    } else {
+        hipLaunchKernelGGL(k_mp_plan<256>, dim3(n, p.plan_groups), dim3(256), 0, sa, b.words, b.desc, n, k, tpp, b.dig,
                            b.idx, b.mp, b.fail, b.counters + CNT_MP_SKIPPED);
+    }
     pad(sa);
-    mark(3, sa);
-    // ---- main stream: VALU-bound hashing
-    if (!fused) {
-        unsigned gx = (unsigned)((rows + 255) / 256);
-        if (gx > 16384) gx = 16384;
+    mark(EV_PLAN_DONE, sa);
+    // ---- main stream: the VALU-bound hashing, and a small batch's FRI
+    if (!p.fused_fs_rows) {
         // dispatch begin / end events (the row kernel's own duration, as the kernel trace has it)
-        hipEvent_t r0 = tm->launch_events ? tm->rev[0] : nullptr, r1 = tm->launch_events ? tm->rev[1] : nullptr;
-        if (n <= rows_wide_max())
-            launch_ev(k_hash_rows_wide<MW>, dim3((unsigned)((rows * 16 + 255) / 256), 3), dim3(256), 0, st,
-                                  r0, r1, b.words, b.desc, n, k, b.dims, b.dig, b.fail);
+        hipEvent_t r0 = p.rows_timed ? tm->rev[0] : nullptr, r1 = p.rows_timed ? tm->rev[1] : nullptr;
+        if (p.rows_wide)
+            launch_ev(k_hash_rows_wide<MW>, dim3(p.rows_grid, 3), dim3(256), 0, st, r0, r1, b.words, b.desc, n, k, b.dims,
+                      b.dig, b.fail);
         else
-            launch_ev(k_hash_rows<MW>, dim3(gx, 3), dim3(256), 0, st, r0, r1, b.words, b.desc, n, k,
-                                  b.dims, b.dig, b.fail, age);
+            launch_ev(k_hash_rows<MW>, dim3(p.rows_grid, 3), dim3(256), 0, st, r0, r1, b.words, b.desc, n, k, b.dims,
+                      b.dig, b.fail, age);
     }
     pad(st);
-    mark(2, st);
-    if (small && fused2) {
-        mark(7, st);  // FRI ran with the plan
-    } else if (small) {
-        wait(st, 1);  // sponge replay done
-        mark(13, st);
-        hipLaunchKernelGGL(k_fri<MW>, dim3(n), dim3(256), 0, st, b.words, b.desc, n, b.dims, b.xs, b.idx, b.xdom, b.fail);
-        pad(st);
-        mark(7, st);
-    }
-    wait(st, 3);  // plan done
-    // The OOD / FRI / DEEP chain only needs the Fiat-Shamir samples, but its kernels are latency-bound
-    // and hold CU resources for long; started after the first `aux_after_level` (wide, VALU-bound)
-    // hash levels it overlaps the narrow, latency-bound top levels instead.
-    auto launch_aux_chain = [&]() {
-        mark(10, st);
-        if (!small) wait(sa, 10);  // small: OOD right after the plan
-        mark(11, sa);
-#define NHIP_OOD_LAUNCH(BLK, GS, THREADS)                                                                       \
-    hipLaunchKernelGGL((k_ood_air<BLK, MW, GS>), dim3(n), dim3(THREADS), b.air_lds_bytes, sa, b.words, b.desc, n,    \
-                       b.dims, b.air_prog, b.air_prog_off, b.air_n_levels, b.air_consts, b.air_cons_off, b.xs, b.ood, \
-                       b.fail, b.air_lds_slots, b.air_gslots, b.air_gslot_n)
-        const bool gs = b.air_gslot_n > 0;
-        if (ood_wide(n)) {
-            if (gs) NHIP_OOD_LAUNCH(1024, true, 1024);
-            else NHIP_OOD_LAUNCH(1024, false, 1024);
-        } else {
-            if (gs) NHIP_OOD_LAUNCH(256, true, b.air_block);
-            else NHIP_OOD_LAUNCH(256, false, b.air_block);
+    mark(EV_ROWS_DONE, st);
+    auto fri = [&](hipStream_t s) {
+        hipLaunchKernelGGL(k_fri<MW>, dim3(n), dim3(256), 0, s, b.words, b.desc, n, b.dims, b.xs, b.idx, b.xdom, b.fail);
+    };
+    if (p.fri_on_main) {
+        if (!p.fused_plan_fri) {
+            wait(st, EV_FS_DONE);  // FRI needs only the sponge samples
+            mark(EV_FRI_START, st);
+            fri(st);
+            pad(st);
         }
-#undef NHIP_OOD_LAUNCH
-        pad(sa);
-        mark(6, sa);
-        if (small) {
-            wait(sa, 7);  // FRI done (main stream)
+        mark(EV_FRI_DONE, st);  // fused: FRI ran with the plan
+    }
+    wait(st, EV_PLAN_DONE);
+    // ---- the aux stream's OOD / FRI / DEEP chain, released from the main stream at the plan's step
+    auto aux_chain = [&]() {
+        mark(EV_AUX_RELEASE, st);
+        if (!p.fri_on_main) wait(sa, EV_AUX_RELEASE);  // FRI on the main stream: OOD right after the plan
+        mark(EV_AUX_START, sa);
+        if (p.ood_block == 1024) {
+            if (p.ood_global_slots) ood(k_ood_air<1024, MW, true>);
+            else ood(k_ood_air<1024, MW, false>);
         } else {
-            hipLaunchKernelGGL(k_fri<MW>, dim3(n), dim3(256), 0, sa, b.words, b.desc, n, b.dims, b.xs, b.idx, b.xdom, b.fail);
-            mark(7, sa);
+            if (p.ood_global_slots) ood(k_ood_air<256, MW, true>);
+            else ood(k_ood_air<256, MW, false>);
+        }
+        pad(sa);
+        mark(EV_OOD_DONE, sa);
+        if (p.fri_on_main) {
+            wait(sa, EV_FRI_DONE);
+        } else {
+            fri(sa);
+            mark(EV_FRI_DONE, sa);
         }
         hipLaunchKernelGGL(k_deep_rows8<MW>, dim3(n), dim3(256), deep_rows8_lds_bytes(b.dims), sa, b.words, b.desc, n,
                            b.dims, b.xs, b.xdom, b.ood, b.fail);
         pad(sa);
-        mark(8, sa);
+        mark(EV_DEEP_DONE, sa);
     };
-    uint32_t launches = 0;
-    bool aux_started = false;
-    if (small) {  // every tree climbed by its own workgroup, one launch
-        launch_aux_chain();
-        aux_started = true;
-        const bool timed = tm->launch_events && tm->lev[0] != nullptr;
-        launch_ev(k_mp_climb<MW>, dim3(n, tpp + 1), dim3(MP_CLIMB_THREADS), 0, st,
-                              timed ? tm->lev[0] : nullptr, timed ? tm->lev[1] : nullptr, b.words, b.dig, b.mp,
-                              tpp, b.desc, n, (const uint32_t*)b.fail, LcwTree{b.lcw, b.max_lcw}, 0u);
-        pad(st);
-        launches = 1;
-    }
-    const LcwTree lcw{b.lcw, b.max_lcw};
-    const uint32_t log2_lcw = 31 - __builtin_clz(b.max_lcw);
-    const uint32_t hash_levels = b.mp.levels > log2_lcw ? b.mp.levels : log2_lcw;
-    static const uint32_t mp_small_max = [] {
-        const char* v = nhip::ab_env("NHIP_MP_SMALL_MAX");
-        return v ? (uint32_t)std::strtoul(v, nullptr, 10) : MP_SMALL_MAX_PROOFS;
-    }();
-    // first level of the tail climbed in one launch (every level from it on is small)
-    uint32_t tail0 = hash_levels;
-    while (tail0 > 0 && hash_levels - tail0 < MP_TAIL_LEVELS_MAX) {
-        const uint32_t l = tail0 - 1;
-        const uint64_t ops = (l < b.mp.levels ? b.mp_cap_host[l] : 0) + (uint64_t)(b.max_lcw >> (l + 1)) * n;
-        if (ops > MP_TAIL_MAX_OPS) break;
-        --tail0;
-    }
-    if (hash_levels - tail0 < 2) tail0 = hash_levels;  // a single small level: the per-level launch
-    for (uint32_t l = 0; l < hash_levels && !small; ++l) {
-        if (!aux_started && (l >= tm->aux_after_level || l == tail0)) {  // the tail is one workgroup
-            launch_aux_chain();
-            aux_started = true;
-        }
-        const bool timed = tm->launch_events && launches < MAX_HASH_LAUNCHES && tm->lev[0] != nullptr;
-        hipEvent_t e0 = timed ? tm->lev[2 * launches] : nullptr, e1 = timed ? tm->lev[2 * launches + 1] : nullptr;
-        {
-            // the rest of every tree climbed per (proof, tree group) in one launch once a level is small
-            // (deep trees: climb_from_ops above)
-            const uint64_t ops_l = (l < b.mp.levels ? b.mp_cap_host[l] : 0) + (uint64_t)(b.max_lcw >> (l + 1)) * n;
-            const uint64_t cf = climb_from_ops(hash_levels);
-            if (cf && ops_l <= cf && hash_levels - l >= 3) {
-                launch_ev(k_mp_climb<MW>, dim3(n, tpp + 1), dim3(MP_CLIMB_THREADS), 0, st, e0, e1, b.words,
-                                      b.dig, b.mp, tpp, b.desc, n, (const uint32_t*)b.fail, lcw, l);
-                ++launches;
+    // ---- main stream: the Merkle levels
+    auto climb = [&](const HashStep& h) {
+        launch_ev(k_mp_climb<MW>, dim3(h.grid, tpp + 1), dim3(MP_CLIMB_THREADS), 0, st, timed(h, 0), timed(h, 1), b.words,
+                  b.dig, b.mp, tpp, b.desc, n, (const uint32_t*)b.fail, lcw, h.level);
+    };
+    for (uint32_t s = 0; s < p.n_steps; ++s) {
+        if (s == p.aux_release_step) aux_chain();
+        const HashStep& h = p.steps[s];
+        switch (h.kind) {
+            case HashKind::Climb: climb(h); break;
+            case HashKind::Tail: {
+                TailCaps caps{};
+                for (uint32_t t = 0; t < MP_TAIL_LEVELS_MAX; ++t) caps.cap[t] = p.tail_caps[t];
+                launch_ev(k_mp_hash_tail<MW>, dim3(h.grid), dim3(MP_TAIL_THREADS), 0, st, timed(h, 0), timed(h, 1), b.words,
+                          b.dig, b.mp, h.level, p.hash_levels, caps, b.desc, n, (const uint32_t*)b.fail, lcw);
                 break;
             }
+            case HashKind::Wide:
+                launch_ev(k_mp_hash_wide<MW>, dim3(h.grid), dim3(256), 0, st, timed(h, 0), timed(h, 1), b.words, b.dig,
+                          b.mp, h.level, h.arg, b.desc, n, (const uint32_t*)b.fail, lcw);
+                break;
+            case HashKind::Level7:
+                launch_ev((k_mp_hash<NHIP_MP_WAVES_SMALL, MW>), dim3(h.grid), dim3(256), 0, st, timed(h, 0), timed(h, 1),
+                          b.words, b.dig, b.mp, h.level, (uint32_t)h.arg, b.desc, n, (const uint32_t*)b.fail, lcw, age);
+                break;
+            case HashKind::Level6:
+                launch_ev((k_mp_hash<NHIP_MP_WAVES, MW>), dim3(h.grid), dim3(256), 0, st, timed(h, 0), timed(h, 1),
+                          b.words, b.dig, b.mp, h.level, (uint32_t)h.arg, b.desc, n, (const uint32_t*)b.fail, lcw, age);
+                break;
         }
-        if (l == tail0) {
-            TailCaps caps{};
-            for (uint32_t t = l; t < hash_levels; ++t) caps.cap[t - l] = t < b.mp.levels ? (uint32_t)b.mp_cap_host[t] : 0u;
-            launch_ev(k_mp_hash_tail<MW>, dim3(1), dim3(MP_TAIL_THREADS), 0, st, e0, e1, b.words, b.dig,
-                                  b.mp, l, hash_levels, caps, b.desc, n, (const uint32_t*)b.fail, lcw);
-            ++launches;
-            break;
-        }
-        const uint64_t cap = l < b.mp.levels ? b.mp_cap_host[l] : 0;
-        const uint32_t mp_blocks = (uint32_t)((cap + 255) / 256);
-        const uint64_t per = b.max_lcw >> (l + 1);
-        const uint32_t lcw_blocks = (uint32_t)((per * n + 255) / 256);
-        if (mp_blocks + lcw_blocks == 0) continue;
-        const bool wide = cap + per * n <= MP_WIDE_MAX_OPS;
-        // hipExtLaunchKernel's start / stop events take the dispatch's own begin / end timestamps
-        // (what the rocprofv3 kernel trace reports): the launch's duration without the dispatch
-        // gap before it, which a plain event pair around back-to-back launches would also hold
-        if (wide)
-            launch_ev(k_mp_hash_wide<MW>, dim3((unsigned)(((cap + per * n) * 16 + 255) / 256)), dim3(256), 0,
-                                  st, e0, e1, b.words, b.dig, b.mp, l, cap, b.desc, n, (const uint32_t*)b.fail, lcw);
-        else if (n < mp_small_max)
-            launch_ev((k_mp_hash<NHIP_MP_WAVES_SMALL, MW>), dim3(mp_blocks + lcw_blocks), dim3(256), 0, st, e0,
-                                  e1, b.words, b.dig, b.mp, l, mp_blocks, b.desc, n, (const uint32_t*)b.fail, lcw, age);
-        else
-            launch_ev((k_mp_hash<NHIP_MP_WAVES, MW>), dim3(mp_blocks + lcw_blocks), dim3(256), 0, st, e0, e1,
-                                  b.words, b.dig, b.mp, l, mp_blocks, b.desc, n, (const uint32_t*)b.fail, lcw, age);
-        ++launches;
     }
-    if (!aux_started) launch_aux_chain();
-    tm->mp_hash_launches = launches;
-    mark(4, st);
-    const uint32_t nrec = n * tpp;
-    if (!two && nrec + n <= ROOTS_ONE_WG) {  // one stream (the aux chain is already in order): one launch
-        hipLaunchKernelGGL(k_roots_verdicts_small<MW>, dim3(1), dim3(ROOTS_ONE_WG), 0, st, b.words, b.desc, b.dig,
-                           b.mp, nrec, tpp, k, b.fail, n, lcw, b.verdicts);
-        mark(5, st);
+    if (p.one_climb) pad(st);
+    if (p.aux_release_step == p.n_steps) aux_chain();
+    mark(EV_HASH_DONE, st);
+    // ---- roots, join, verdicts
+    if (p.roots_one_launch) {
+        hipLaunchKernelGGL(k_roots_verdicts_small<MW>, dim3(p.roots_grid), dim3(ROOTS_ONE_WG), 0, st, b.words, b.desc,
+                           b.dig, b.mp, p.n_records, tpp, k, b.fail, n, lcw, b.verdicts);
+        mark(EV_ROOTS_DONE, st);
     } else {
-        hipLaunchKernelGGL(k_mp_roots<MW>, dim3((nrec + n + 255) / 256), dim3(256), 0, st, b.words, b.desc, b.dig,
-                           b.mp, nrec, tpp, k, b.fail, n, lcw);
+        hipLaunchKernelGGL(k_mp_roots<MW>, dim3(p.roots_grid), dim3(256), 0, st, b.words, b.desc, b.dig, b.mp,
+                           p.n_records, tpp, k, b.fail, n, lcw);
         pad(st);
-        mark(5, st);
-        wait(st, 8);  // join the aux chain
-        hipLaunchKernelGGL(k_verdicts, dim3((n + 255) / 256), dim3(256), 0, st, b.fail, n, b.verdicts);
+        mark(EV_ROOTS_DONE, st);
+        wait(st, EV_DEEP_DONE);  // join the aux chain
+        hipLaunchKernelGGL(k_verdicts, dim3(p.verdicts_grid), dim3(256), 0, st, b.fail, n, b.verdicts);
     }
-    mark(9, st);
+    mark(EV_VERDICTS, st);
     return hipGetLastError();
 }
 

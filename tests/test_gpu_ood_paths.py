@@ -18,7 +18,7 @@ import tip5_ref as T
 pytestmark = pytest.mark.gpu
 
 FAIL_OOD = 1 << 1
-WIDE_MAX = 64  # OOD_WIDE_MAX_PROOFS (kernels.hpp)
+WIDE_MAX = 64  # OOD_WIDE_MAX_PROOFS (stark_launch_plan.hpp)
 
 
 def _transcript(params, air, claim, proof):
