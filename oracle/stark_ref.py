@@ -524,9 +524,15 @@ class SynthRecipe:
 
 
 def synth_air(params: StarkParams, num_sampled: int = CHALLENGE_SAMPLE_COUNT, seed: int = 0x5EED, num_constraints: Optional[int] = None):
-    """Deterministic synthetic AIR with params' column counts (see module doc)."""
+    """Deterministic synthetic AIR with params' column counts (see module doc).
+
+    Smallest shape: num_main >= 5 (four free columns the constraints read and the unconstrained last
+    one) and num_aux >= 1; fewer raise ValueError.  With fewer than NUM_DERIVED_CHALLENGES aux columns
+    only the last num_aux derived challenges are bound."""
     rng = _SplitMix(seed)
     M, A = params.num_main, params.num_aux
+    if M < 5 or A < 1:
+        raise ValueError(f"synth_air: num_main >= 5 and num_aux >= 1, got {M} and {A}")
     nodes: List[Tuple[int, int, int, int]] = []
     cache: Dict[tuple, int] = {}
 
@@ -626,6 +632,13 @@ def synth_air(params: StarkParams, num_sampled: int = CHALLENGE_SAMPLE_COUNT, se
             by_type[ctype].append(recipe.targets[ti]["node"])
     # combination constraints C = C_a + lambda * C_b (same zerofier type) up to the requested count
     want = num_constraints if num_constraints is not None else max(len(recipe.targets), int(1.6 * len(recipe.targets)))
+    if all(len(b) < 2 for b in base_by_type):
+        # a combination needs two base constraints of one zerofier type; a very small AIR (M = 7,
+        # A = 1: three targets, often of three types) may have no such pair, and the loop below would
+        # draw types for ever
+        if num_constraints is not None and want > len(recipe.targets):
+            raise ValueError("synth_air: no two base constraints share a type, so none can be combined")
+        want = len(recipe.targets)
     while sum(len(c) for c in by_type) < want:
         ctype = pick_type()
         if len(base_by_type[ctype]) < 2:
