@@ -10,6 +10,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #include "../../include/nhip_challenge_id.h"
 #include "kernels.hpp"
@@ -333,14 +334,23 @@ __global__ void __launch_bounds__(1024) k_fs_replay_quad(const uint64_t* __restr
 #ifndef NHIP_ROWS_WAVES
 #define NHIP_ROWS_WAVES 5
 #endif
-template <bool MW>
-__global__ void __launch_bounds__(256, NHIP_ROWS_WAVES) k_hash_rows(const uint64_t* __restrict__ words, const ProofDesc* __restrict__ desc,
+// PLANES: the full rounds' MDS on the matrix cores (mds_ark_planes); its two sums in flight, the
+// byte planes and the constant tiles need more registers than the VALU form's groups of four:
+// 128 VGPRs and 48 B of scratch at 4 waves.  3 waves (no scratch): config 4 0.7% slower at 4,096
+// proofs, 1% faster at 512 (profiles/r09a).  Launched for batches of ROWS_PLANES_MIN_PROOFS and more.
+#ifndef NHIP_ROWS_WAVES_PLANES
+#define NHIP_ROWS_WAVES_PLANES 4
+#endif
+template <bool MW, bool PLANES>
+__global__ void __launch_bounds__(256, PLANES ? NHIP_ROWS_WAVES_PLANES : NHIP_ROWS_WAVES) k_hash_rows(const uint64_t* __restrict__ words, const ProofDesc* __restrict__ desc,
                                                    uint32_t n_proofs, uint32_t k, StarkDims dims,
                                                    uint64_t* __restrict__ dig, const uint32_t* __restrict__ fail,
                                                    AgePrio age) {
     age_priority(age, 0);
     __shared__ Tip5Lds lds;
     tip5_lds_init(lds);
+    std::conditional_t<PLANES, Tip5Planes, Tip5NoPlanes> pl;
+    if constexpr (PLANES) tip5_planes_init(pl);  // every lane, before any leaves the loop
     const uint32_t tree = blockIdx.y;
     const uint32_t width = tree == 0 ? dims.num_main : (tree == 1 ? 3 * dims.num_aux : 3 * dims.num_quot_seg);
     for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < (uint64_t)n_proofs * k;
@@ -372,7 +382,7 @@ __global__ void __launch_bounds__(256, NHIP_ROWS_WAVES) k_hash_rows(const uint64
                     s[q] = qq < rem ? word_mont<MW>(row[pos + qq]) : (qq == rem ? MONT_ONE : 0ull);
                 }
             }
-            tip5_rounds_0_3(s, lds.lut);
+            tip5_rounds_0_3(s, lds.lut, pl);
             tip5_last_sbox(s, lds.lut);
             if (!last) tip5_last_mds<10, 16>(s);
             else tip5_last_mds<0, 5>(s);
@@ -783,8 +793,16 @@ __device__ __forceinline__ void lcw_node(const uint64_t* __restrict__ words, con
 #ifndef NHIP_MP_WAVES_SMALL
 #define NHIP_MP_WAVES_SMALL 7
 #endif
-template <int WAVES, bool MW>
-__global__ void __launch_bounds__(256, WAVES) k_mp_hash(const uint64_t* __restrict__ words, const uint64_t* __restrict__ dig,
+// PLANES: rounds 1-3 of the pair hash with the MDS on the matrix cores, at NHIP_MP_WAVES_PLANES
+// waves for either instance (the planes form's registers, see k_hash_rows).  Off, and instantiated
+// in A/B builds only (NHIP_MDS_PLANES_MP=1): three of the pair hash's five rounds take the form,
+// and 4 waves instead of 6 / 7 cost what they save (profiles/r09a: the Merkle levels equal at
+// 4,096 proofs, 20% slower at 512).
+#ifndef NHIP_MP_WAVES_PLANES
+#define NHIP_MP_WAVES_PLANES 4
+#endif
+template <int WAVES, bool MW, bool PLANES>
+__global__ void __launch_bounds__(256, PLANES ? NHIP_MP_WAVES_PLANES : WAVES) k_mp_hash(const uint64_t* __restrict__ words, const uint64_t* __restrict__ dig,
                                                  MpPlan plan, uint32_t lvl, uint32_t mp_blocks,
                                                  const ProofDesc* __restrict__ desc, uint32_t n_proofs,
                                                  const uint32_t* __restrict__ fail, LcwTree lcw, AgePrio age) {
@@ -802,6 +820,8 @@ __global__ void __launch_bounds__(256, WAVES) k_mp_hash(const uint64_t* __restri
             s_base[MP_SHARDS] = plan.shard_base[(lvl + 1) * MP_SHARDS - 1] + plan.shard_cap[(lvl + 1) * MP_SHARDS - 1];
     }
     tip5_lds_init(t5);  // includes the barrier
+    std::conditional_t<PLANES, Tip5Planes, Tip5NoPlanes> pl;
+    if constexpr (PLANES) tip5_planes_init(pl);  // every lane, before the idle ones return
     uint64_t s[16];
     uint64_t* o = nullptr;
     bool work = false;
@@ -839,7 +859,7 @@ __global__ void __launch_bounds__(256, WAVES) k_mp_hash(const uint64_t* __restri
         }
     }
     if (!work) return;
-    tip5_hash_pair_digest(s, t5.lut);  // capacity 1: FixedLength domain
+    tip5_hash_pair_digest(s, t5.lut, pl);  // capacity 1: FixedLength domain
 #pragma unroll
     for (int q = 0; q < 5; ++q) o[q] = s[q];
 }
@@ -1891,8 +1911,8 @@ static hipError_t launch_phases(const StarkBatchDev& b, hipStream_t st, hipStrea
             launch_ev(k_hash_rows_wide<MW>, dim3(p.rows_grid, 3), dim3(256), 0, st, r0, r1, b.words, b.desc, n, k, b.dims,
                       b.dig, b.fail);
         else
-            launch_ev(k_hash_rows<MW>, dim3(p.rows_grid, 3), dim3(256), 0, st, r0, r1, b.words, b.desc, n, k, b.dims,
-                      b.dig, b.fail, age);
+            launch_ev(n >= kn.rows_planes_min ? k_hash_rows<MW, true> : k_hash_rows<MW, false>, dim3(p.rows_grid, 3), dim3(256), 0,
+                      st, r0, r1, b.words, b.desc, n, k, b.dims, b.dig, b.fail, age);
     }
     pad(st);
     mark(EV_ROWS_DONE, st);
@@ -1935,6 +1955,12 @@ static hipError_t launch_phases(const StarkBatchDev& b, hipStream_t st, hipStrea
         mark(EV_DEEP_DONE, sa);
     };
     // ---- main stream: the Merkle levels
+#ifdef NHIP_AB_BUILD
+    constexpr bool MP_PLANES_BUILT = true;
+#else
+    constexpr bool MP_PLANES_BUILT = false;
+#endif
+    const bool mp_planes = MP_PLANES_BUILT && kn.mds_planes_mp;
     auto climb = [&](const HashStep& h) {
         launch_ev(k_mp_climb<MW>, dim3(h.grid, tpp + 1), dim3(MP_CLIMB_THREADS), 0, st, timed(h, 0), timed(h, 1), b.words,
                   b.dig, b.mp, tpp, b.desc, n, (const uint32_t*)b.fail, lcw, h.level);
@@ -1956,11 +1982,11 @@ static hipError_t launch_phases(const StarkBatchDev& b, hipStream_t st, hipStrea
                           b.mp, h.level, h.arg, b.desc, n, (const uint32_t*)b.fail, lcw);
                 break;
             case HashKind::Level7:
-                launch_ev((k_mp_hash<NHIP_MP_WAVES_SMALL, MW>), dim3(h.grid), dim3(256), 0, st, timed(h, 0), timed(h, 1),
+                launch_ev(mp_planes ? k_mp_hash<NHIP_MP_WAVES_SMALL, MW, MP_PLANES_BUILT> : k_mp_hash<NHIP_MP_WAVES_SMALL, MW, false>, dim3(h.grid), dim3(256), 0, st, timed(h, 0), timed(h, 1),
                           b.words, b.dig, b.mp, h.level, (uint32_t)h.arg, b.desc, n, (const uint32_t*)b.fail, lcw, age);
                 break;
             case HashKind::Level6:
-                launch_ev((k_mp_hash<NHIP_MP_WAVES, MW>), dim3(h.grid), dim3(256), 0, st, timed(h, 0), timed(h, 1),
+                launch_ev(mp_planes ? k_mp_hash<NHIP_MP_WAVES, MW, MP_PLANES_BUILT> : k_mp_hash<NHIP_MP_WAVES, MW, false>, dim3(h.grid), dim3(256), 0, st, timed(h, 0), timed(h, 1),
                           b.words, b.dig, b.mp, h.level, (uint32_t)h.arg, b.desc, n, (const uint32_t*)b.fail, lcw, age);
                 break;
         }

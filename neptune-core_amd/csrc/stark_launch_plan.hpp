@@ -32,6 +32,11 @@ static constexpr uint32_t FS_PAIR_MAX_PROOFS = 512;
 // 1,024 threads -1 to -25% (profiles/r03g, 2 repetitions)
 static constexpr uint32_t FS_QUAD_MIN_PROOFS = 2048;
 static constexpr uint32_t FS_QUAD_WG = 256;  // k_fs_replay_quad workgroup size
+// batches of at least this many proofs hash their revealed rows with the full rounds' MDS on the matrix
+// cores (k_hash_rows<MW, true>, tip5_device.hpp mds_ark_planes): measured faster at 512, 1,024, 2,048 and
+// 4,096 proofs (profiles/r09a); smaller batches, where a few waves per SIMD wait on one permutation's
+// dependent chain, keep the VALU form
+static constexpr uint32_t ROWS_PLANES_MIN_PROOFS = 512;
 // batches below this many proofs hash their Merkle levels with the 7-wave k_mp_hash instance, larger
 // ones with the 6-wave one.  7 waves: 2,048 proofs +1.3%, 1,024 +1.2%, 512 +3%; 4,096 -0.6%
 // (profiles/r03ze, r03zf)
@@ -86,6 +91,8 @@ struct LaunchKnobs {
     uint32_t climb_max = MP_CLIMB_MAX_PROOFS;           // NHIP_CLIMB_MAX
     uint32_t aux_after_level = AUX_AFTER_LEVEL_DEFAULT;  // NHIP_AUX_AFTER_LEVEL
     int pad_packets = 0;  // NHIP_PAD_PACKETS: empty kernels after each kernel of the batch
+    uint32_t rows_planes_min = ROWS_PLANES_MIN_PROOFS;  // NHIP_ROWS_PLANES_MIN (a huge value: never)
+    bool mds_planes_mp = false;  // NHIP_MDS_PLANES_MP=1: k_mp_hash with the planes MDS in rounds 1-3 (A/B builds only)
 };
 
 inline unsigned long ab_unsigned(const char* name, unsigned long dflt) {
@@ -110,6 +117,8 @@ inline LaunchKnobs launch_knobs_from_env() {
     kn.climb_max = (uint32_t)ab_unsigned("NHIP_CLIMB_MAX", kn.climb_max);
     kn.aux_after_level = (uint32_t)ab_unsigned("NHIP_AUX_AFTER_LEVEL", kn.aux_after_level);
     kn.pad_packets = (int)ab_unsigned("NHIP_PAD_PACKETS", 0);
+    kn.rows_planes_min = (uint32_t)ab_unsigned("NHIP_ROWS_PLANES_MIN", kn.rows_planes_min);
+    if (const char* e = ab_env("NHIP_MDS_PLANES_MP")) kn.mds_planes_mp = e[0] == '1';
     return kn;
 }
 inline const LaunchKnobs& launch_knobs() {

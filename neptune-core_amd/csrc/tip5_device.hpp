@@ -16,6 +16,7 @@
 #pragma once
 #include "goldilocks.hpp"
 #include "tip5_constants.h"
+#include "tip5_mds_planes.hpp"
 
 namespace nhip {
 
@@ -313,14 +314,177 @@ __device__ __forceinline__ void mds_ark(uint64_t s[16], const uint64_t* __restri
     mds_ark_fold<16, 0, 16, G>(s, rck);
 }
 
+// ---------------------------------------------------------------------------------------------
+// MDS + ARK on the matrix cores, as byte planes (tip5_mds_planes.hpp has the arithmetic and its
+// ranges; tests/native/mds_planes_check.cpp runs it in host integers).  The state stays on its
+// lane: its 128 bytes, offset to signed by one XOR per dword, are transposed into 8 planes of 16
+// bytes (plane d = byte d of words 0..15, 8 v_perm_b32 per four words), each plane is the B
+// operand of v_mfma_i32_32x32x32_i8 against one of three constant A tiles (the circulant's digits,
+// zero where a row meets the other lane half's bytes), and register r of the 32 x 32 result is
+// output r of the lane's own state.  24 MFMAs give C_0 .. C_9; eight multiply-adds per word by
+// 1, 2^8, 2^16, 2^24 rebuild the accumulator pair mds_fold4 reduces.
+// ---------------------------------------------------------------------------------------------
+typedef int tip5_v4i __attribute__((ext_vector_type(4)));
+typedef int tip5_v16i __attribute__((ext_vector_type(16)));
+
+struct Tip5PlanesTable {
+    uint32_t w[3 * 64 * 4];  // tile e, lane l: 4 dwords (bytes t = 0..15 of planes_tile_byte)
+};
+constexpr Tip5PlanesTable tip5_planes_table() {
+    Tip5PlanesTable tb{};
+    for (int e = 0; e < 3; ++e)
+        for (int l = 0; l < 64; ++l)
+            for (int t = 0; t < 16; ++t)
+                tb.w[(e * 64 + l) * 4 + t / 4] |= (uint32_t)(uint8_t)(int8_t)planes_tile_byte(e, l, t) << (8 * (t % 4));
+    return tb;
+}
+__constant__ static Tip5PlanesTable c_tip5_planes_tiles = tip5_planes_table();
+
+// the planes form's low-accumulator starts (planes_start of K = RC + 2^32 - 1), as c_tip5_rck_raw
+__constant__ static uint64_t c_tip5_rckp_raw[80] = {
+#define NHIP_RC(i) planes_start(TIP5_RC_RAW[i] + 0xFFFFFFFFull)
+    NHIP_RC(0), NHIP_RC(1), NHIP_RC(2), NHIP_RC(3), NHIP_RC(4), NHIP_RC(5), NHIP_RC(6), NHIP_RC(7),
+    NHIP_RC(8), NHIP_RC(9), NHIP_RC(10), NHIP_RC(11), NHIP_RC(12), NHIP_RC(13), NHIP_RC(14), NHIP_RC(15),
+    NHIP_RC(16), NHIP_RC(17), NHIP_RC(18), NHIP_RC(19), NHIP_RC(20), NHIP_RC(21), NHIP_RC(22), NHIP_RC(23),
+    NHIP_RC(24), NHIP_RC(25), NHIP_RC(26), NHIP_RC(27), NHIP_RC(28), NHIP_RC(29), NHIP_RC(30), NHIP_RC(31),
+    NHIP_RC(32), NHIP_RC(33), NHIP_RC(34), NHIP_RC(35), NHIP_RC(36), NHIP_RC(37), NHIP_RC(38), NHIP_RC(39),
+    NHIP_RC(40), NHIP_RC(41), NHIP_RC(42), NHIP_RC(43), NHIP_RC(44), NHIP_RC(45), NHIP_RC(46), NHIP_RC(47),
+    NHIP_RC(48), NHIP_RC(49), NHIP_RC(50), NHIP_RC(51), NHIP_RC(52), NHIP_RC(53), NHIP_RC(54), NHIP_RC(55),
+    NHIP_RC(56), NHIP_RC(57), NHIP_RC(58), NHIP_RC(59), NHIP_RC(60), NHIP_RC(61), NHIP_RC(62), NHIP_RC(63),
+    NHIP_RC(64), NHIP_RC(65), NHIP_RC(66), NHIP_RC(67), NHIP_RC(68), NHIP_RC(69), NHIP_RC(70), NHIP_RC(71),
+    NHIP_RC(72), NHIP_RC(73), NHIP_RC(74), NHIP_RC(75), NHIP_RC(76), NHIP_RC(77), NHIP_RC(78), NHIP_RC(79),
+#undef NHIP_RC
+};
+
+// What a lane keeps for the planes form: its fragments of the three constant tiles, and the
+// powers of two as register values the compiler cannot see through (so that C * 2^8k + addend stays
+// one v_mad_i64_i32 instead of a shift, a sign extension and a 64-bit add).
+struct Tip5Planes {
+    tip5_v4i tile[3];
+    int32_t k0, k8, k16, k24;
+};
+// Every lane of the wave must run this (the MFMA reads the A fragments of all 64 lanes, whatever
+// EXEC is later): call it before any lane leaves the kernel.
+__device__ __forceinline__ void tip5_planes_init(Tip5Planes& pl) {
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const tip5_v4i* tb = (const tip5_v4i*)c_tip5_planes_tiles.w;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        pl.tile[e] = tb[e * 64 + lane];
+        asm volatile("" : "+v"(pl.tile[e]));  // the load stays here, where every lane is active
+    }
+    asm("v_mov_b32 %0, 1" : "=v"(pl.k0));
+    asm("s_mov_b32 %0, 0x100" : "=s"(pl.k8));
+    asm("s_mov_b32 %0, 0x10000" : "=s"(pl.k16));
+    asm("s_mov_b32 %0, 0x1000000" : "=s"(pl.k24));
+}
+
+// C_Q of the 16 outputs: the (e, d = Q - e) products chained in one accumulator
+template <int Q>
+__device__ __forceinline__ tip5_v16i planes_cq(const Tip5Planes& pl, const tip5_v4i* plane) {
+    tip5_v16i c = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < 3; ++e)
+        if (Q - e >= 0 && Q - e <= 7) c = __builtin_amdgcn_mfma_i32_32x32x32_i8(pl.tile[e], plane[Q - e], c, 0, 0, 0);
+    return c;
+}
+
+__device__ __forceinline__ int64_t planes_mad(int32_t c, int32_t k, int64_t a) { return (int64_t)c * (int64_t)k + a; }
+
+// The order the ten sums are produced and consumed in: the low accumulator (q = 0..3), the high
+// dword (9, 8), then T (4..7), whose start pair is (al >> 32, Hb).  Step K issues the MFMAs of the
+// next sum before it consumes its own, and a scheduling barrier ends it: two sums are in flight,
+// not ten (10 x 16 result registers).
+__host__ __device__ constexpr int planes_order(int k) {
+    constexpr int o[10] = {0, 1, 2, 3, 9, 8, 4, 5, 6, 7};
+    return o[k];
+}
+template <int K>
+__device__ __forceinline__ void planes_step(const Tip5Planes& pl, const tip5_v4i* plane, const tip5_v16i& c,
+                                            const uint64_t* __restrict__ rckp, int64_t* al, int64_t* t, uint32_t* hb) {
+    constexpr int Q = planes_order(K);
+    tip5_v16i next;
+    if constexpr (K < 9) next = planes_cq<planes_order(K + 1)>(pl, plane);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        if constexpr (Q == 0) al[i] = planes_mad(c[i], pl.k0, (int64_t)rckp[i]);
+        if constexpr (Q == 1) al[i] = planes_mad(c[i], pl.k8, al[i]);
+        if constexpr (Q == 2) al[i] = planes_mad(c[i], pl.k16, al[i]);
+        if constexpr (Q == 3) al[i] = planes_mad(c[i], pl.k24, al[i]);
+        if constexpr (Q == 9) hb[i] = ((uint32_t)c[i] << 8) + (uint32_t)PLANES_HB_BIAS;
+        if constexpr (Q == 8) t[i] = (int64_t)(((uint64_t)(hb[i] + (uint32_t)c[i]) << 32) | (uint32_t)((uint64_t)al[i] >> 32));
+        if constexpr (Q == 4) t[i] = planes_mad(c[i], pl.k0, t[i]);
+        if constexpr (Q == 5) t[i] = planes_mad(c[i], pl.k8, t[i]);
+        if constexpr (Q == 6) t[i] = planes_mad(c[i], pl.k16, t[i]);
+        if constexpr (Q == 7) t[i] = planes_mad(c[i], pl.k24, t[i]);
+    }
+    if constexpr (K < 9) {
+        __builtin_amdgcn_sched_barrier(0);
+        planes_step<K + 1>(pl, plane, next, rckp, al, t, hb);
+    }
+}
+
+// s <- MDS(s) + RC of one full round; rckp: the round's 16 starts (c_tip5_rckp_raw)
+__device__ __forceinline__ void mds_ark_planes(uint64_t s[16], const uint64_t* __restrict__ rckp, const Tip5Planes& pl) {
+    tip5_v4i plane[8];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            uint32_t w[4];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) w[b] = (uint32_t)(s[4 * m + b] >> (32 * h)) ^ 0x80808080u;
+            // 4 x 4 byte transpose: (w0.b0 w1.b0 w0.b1 w1.b1), (w0.b2 w1.b2 w0.b3 w1.b3), ...
+            const uint32_t a0 = __builtin_amdgcn_perm(w[1], w[0], 0x05010400u);
+            const uint32_t a1 = __builtin_amdgcn_perm(w[1], w[0], 0x07030602u);
+            const uint32_t c0 = __builtin_amdgcn_perm(w[3], w[2], 0x05010400u);
+            const uint32_t c1 = __builtin_amdgcn_perm(w[3], w[2], 0x07030602u);
+            plane[4 * h + 0][m] = (int)__builtin_amdgcn_perm(c0, a0, 0x05040100u);
+            plane[4 * h + 1][m] = (int)__builtin_amdgcn_perm(c0, a0, 0x07060302u);
+            plane[4 * h + 2][m] = (int)__builtin_amdgcn_perm(c1, a1, 0x05040100u);
+            plane[4 * h + 3][m] = (int)__builtin_amdgcn_perm(c1, a1, 0x07060302u);
+        }
+    int64_t al[16], t[16];
+    uint32_t hb[16];
+    planes_step<0>(pl, plane, planes_cq<0>(pl, plane), rckp, al, t, hb);
+    uint32_t sh[16], e[16];
+    uint64_t slo[16], w[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        sh[i] = (uint32_t)((uint64_t)t[i] >> 32);
+        slo[i] = ((uint64_t)t[i] << 32) | (uint32_t)al[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i += 4) mds_fold4(sh + i, slo + i, w + i, e + i);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s[i] = w[i] - e[i];
+}
+
+// The MDS form of the full rounds is the round functions' template argument PL: Tip5NoPlanes (the
+// default) is mds_ark's VALU form; Tip5Planes, with the caller's tip5_planes_init'ed value, the
+// planes form.  Rounds that skip inputs or outputs (round 0 of hash_pair, every last round of a
+// sponge that keeps part of the state) stay on the VALU form: the planes form cannot skip either.
+struct Tip5NoPlanes {};
+template <class PL>
+inline constexpr bool tip5_is_planes = false;
+template <>
+inline constexpr bool tip5_is_planes<Tip5Planes> = true;
+// full round r's MDS + ARK; G: the VALU form's output group
+template <int G, class PL>
+__device__ __forceinline__ void mds_ark_round(uint64_t s[16], int r, const PL& pl) {
+    if constexpr (tip5_is_planes<PL>) mds_ark_planes(s, c_tip5_rckp_raw + r * 16, pl);
+    else mds_ark<G>(s, c_tip5_rc_raw + r * 16, c_tip5_rck_raw + r * 16);
+}
+
 // One permutation on a raw Montgomery state.
-__device__ __forceinline__ void tip5_permute_raw(uint64_t s[16], const uint8_t* __restrict__ lut) {
+template <class PL = Tip5NoPlanes>
+__device__ __forceinline__ void tip5_permute_raw(uint64_t s[16], const uint8_t* __restrict__ lut, const PL& pl = PL{}) {
 #pragma unroll 1
     for (int r = 0; r < TIP5_ROUNDS; ++r) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) s[i] = split_and_lookup(lut, s[i]);
         pow7_12(s + 4);
-        mds_ark(s, c_tip5_rc_raw + r * 16, c_tip5_rck_raw + r * 16);
+        mds_ark_round<NHIP_SPONGE_MDS_GROUP>(s, r, pl);
     }
 }
 
@@ -355,7 +519,8 @@ __constant__ static uint64_t c_tip5_rck0_fixed[16] = {
 // tip5_permute_raw, the last of them computing the digest words only.  Round 0: 552 fewer VALU
 // instructions (6 x^7 chains of 4 Montgomery products, 6 x 16 x 2 MDS multiply-adds); round 4: ~420
 // fewer (11 of 16 MDS outputs).
-__device__ __forceinline__ void tip5_hash_pair_digest(uint64_t s[16], const uint8_t* __restrict__ lut) {
+template <class PL = Tip5NoPlanes>
+__device__ __forceinline__ void tip5_hash_pair_digest(uint64_t s[16], const uint8_t* __restrict__ lut, const PL& pl = PL{}) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) s[i] = split_and_lookup(lut, s[i]);
 #pragma unroll
@@ -372,7 +537,7 @@ __device__ __forceinline__ void tip5_hash_pair_digest(uint64_t s[16], const uint
 #pragma unroll
         for (int i = 0; i < 4; ++i) s[i] = split_and_lookup(lut, s[i]);
         pow7_12(s + 4);
-        mds_ark<NHIP_PAIR_MDS_GROUP>(s, c_tip5_rc_raw + r * 16, c_tip5_rck_raw + r * 16);
+        mds_ark_round<NHIP_PAIR_MDS_GROUP>(s, r, pl);
     }
     // last round: the caller reads the digest s[0..5] only, so the MDS computes those 5 outputs
     // (11 x 16 x 2 multiply-adds and 11 reductions fewer); s[5..16] are left stale
@@ -386,13 +551,14 @@ __device__ __forceinline__ void tip5_hash_pair_digest(uint64_t s[16], const uint
 // [OBEG, OEND) (the sponge's kept words): hash_varlen's absorbs overwrite the rate s[0..10], so a
 // permutation followed by another absorb needs s[10..16] only (<10, 16>: 10 x 16 x 2 multiply-adds
 // and 10 reductions fewer), and the one before the digest is read needs s[0..5] (<0, 5>).
-__device__ __forceinline__ void tip5_rounds_0_3(uint64_t s[16], const uint8_t* __restrict__ lut) {
+template <class PL = Tip5NoPlanes>
+__device__ __forceinline__ void tip5_rounds_0_3(uint64_t s[16], const uint8_t* __restrict__ lut, const PL& pl = PL{}) {
 #pragma unroll 1
     for (int r = 0; r < TIP5_ROUNDS - 1; ++r) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) s[i] = split_and_lookup(lut, s[i]);
         pow7_12(s + 4);
-        mds_ark(s, c_tip5_rc_raw + r * 16, c_tip5_rck_raw + r * 16);
+        mds_ark_round<NHIP_SPONGE_MDS_GROUP>(s, r, pl);
     }
 }
 // The last round's S-box layer; the caller then keeps the MDS outputs it needs
