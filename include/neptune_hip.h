@@ -730,7 +730,10 @@ enum {
     NHIP_MS_UNPACK_INCONSISTENT_CHUNKS = 16,      /* RemovalRecordListInconsistency::Chunks */
     NHIP_MS_UNPACK_STRUCTURE_COUNT = 17,          /* ...::AuthenticationStructureCount */
     NHIP_MS_UNPACK_STRUCTURE_LENGTH = 18,         /* ...::AuthenticationStructureLength */
-    NHIP_MS_UNPACK_PANIC = 19                     /* the reference panics on this list: fail closed */
+    NHIP_MS_UNPACK_PANIC = 19,                    /* the reference panics on this list: fail closed */
+    /* nhip_ms_update_batch only (a witness's status) */
+    NHIP_MS_JOB_REJECTED = 20,   /* the witness's job did not end NHIP_MS_OK: nothing of it is brought up to date */
+    NHIP_MS_UPDATE_INTERNAL = 21 /* a digest the witness needs was found nowhere it can come from: never a guess */
 };
 /* twenty-first MmrMembershipProof::verify(leaf_index, leaf, peaks, num_leafs) for n (leaf, path)
  * items against one MMR, as called bare in application/loops/peer_loop.rs:1235 and
@@ -847,6 +850,62 @@ int nhip_ms_unpack_batch(nhip_ctx *ctx, const uint64_t *rec_off, size_t n_jobs, 
  * verdict 0, its unpack status, bad_record = UINT64_MAX and zero accumulator counts; the others run exactly as in
  * nhip_ms_apply_batch.  The unpacked paths are produced on the device and never cross to the host. */
 int nhip_ms_apply_batch_packed(nhip_ctx *ctx, const nhip_ms_apply_in *in, nhip_ms_apply_out *out);
+
+/* ---- membership proofs and removal records across a block ----------------------
+ * MsMembershipProof::batch_update_from_addition / batch_update_from_remove (ms_membership_proof.rs:76-270,
+ * 417-468) and RemovalRecord::batch_update_from_addition / batch_update_from_remove (removal_record.rs:49-200)
+ * over a whole block, computed as the end state: a job is a job of nhip_ms_apply_batch plus the witnesses
+ * wit_off[j] .. wit_off[j + 1] to bring up to the accumulator after it.  A witness is an index set, a chunk
+ * dictionary and, for a membership proof, an AOCL part (leaf index, leaf = the addition record's canonical
+ * commitment, authentication path); a removal record has aocl_leaf_index == UINT64_MAX.  With n0 / n1 the
+ * AOCL leaf counts before / after and b0 / b1 the batch indices before / after:
+ *   job:       steps 1-5 of nhip_ms_apply_batch; unless the job ends NHIP_MS_OK every witness of it gets
+ *              NHIP_MS_JOB_REJECTED.
+ *   admission: per witness, the first failure of
+ *              NHIP_MS_NOT_IN_AOCL   (AOCL part only) l >= n1; l < n0 and the path does not authenticate the leaf
+ *                                    against msa_before.aocl; n0 <= l < n1 and the leaf is not additions[l - n0]
+ *                                    or the path is not empty;
+ *              NHIP_MS_OUT_OF_RANGE  minimum + distance saturates u128, or a chunk index exceeds b1 + 255;
+ *              NHIP_MS_ABSENT_CHUNK  the dictionary's keys are not, strictly ascending, exactly the witness's
+ *                                    chunk indices below b0;
+ *              NHIP_MS_BAD_MMR_PATH  an entry does not authenticate against msa_before.swbf_inactive.
+ *              Whether the item is already removed plays no part.
+ *   after:     the AOCL path has ilog2(l ^ n1) digests; the dictionary's keys are the witness's chunk indices
+ *              below b1, ascending, each with the chunk after the block (the old entry's chunk, or the slid part
+ *              of the old window, merged with the block's indices in that chunk, repeats kept) and its path of
+ *              ilog2(key ^ b1) digests in swbf_inactive after the block.
+ * Every output length is an integer function of the inputs, laid out by nhip_ms_update_plan as if every job and
+ * witness were accepted; the slots of a witness whose status is not NHIP_MS_OK keep their planned offsets and
+ * are zero-filled (chunk_index included).  Two-call sizing as nhip_ms_unpack_plan: with every array pointer but
+ * status NULL only the totals are written (and nothing runs on the device). */
+typedef struct {
+    const uint64_t *wit_off;         /* n_jobs + 1, in witnesses */
+    const uint64_t *minimum;         /* witnesses x 2 u64 (u128, little-endian) */
+    const uint32_t *distances;       /* witnesses x 45 */
+    const uint64_t *aocl_leaf_index; /* witnesses; UINT64_MAX: no AOCL part */
+    const uint64_t *aocl_leaf;       /* witnesses x 5 (ignored without an AOCL part) */
+    const uint64_t *aocl_path_off;   /* witnesses + 1, in digests */
+    const uint64_t *aocl_path;
+    const nhip_ms_chunks *chunks;    /* the dictionaries of all witnesses */
+} nhip_ms_update_in;
+typedef struct {
+    uint8_t *status;         /* witnesses: NHIP_MS_*; nhip_ms_update_plan leaves it alone */
+    uint64_t *aocl_path_off; /* witnesses + 1, in digests */
+    uint64_t *aocl_path;     /* aocl_cap digests; the plan leaves it alone */
+    uint64_t *entry_off;     /* witnesses + 1 */
+    uint64_t *chunk_index;   /* entries_cap */
+    uint64_t *path_off;      /* entries_cap + 1, in digests */
+    uint64_t *path;          /* path_cap digests; the plan leaves it alone */
+    uint64_t *rel_off;       /* entries_cap + 1, in u32 */
+    uint32_t *rel;           /* rel_cap; the plan leaves it alone */
+    size_t aocl_cap, entries_cap, path_cap, rel_cap;
+    size_t aocl_digests, entries, path_digests, rel_words; /* out: the totals */
+} nhip_ms_updated;
+/* The shape alone (no context, host only, hashes nothing): the four offset arrays and the keys. */
+int nhip_ms_update_plan(const nhip_ms_apply_in *block, const nhip_ms_update_in *wit, nhip_ms_updated *out);
+/* block_out is filled as nhip_ms_apply_batch fills it.  Shape errors are NHIP_ERR_ARG with the outputs untouched. */
+int nhip_ms_update_batch(nhip_ctx *ctx, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out,
+                         const nhip_ms_update_in *wit, nhip_ms_updated *out);
 
 /* ---- kernel timing (HIP events on the ctx stream around every kernel launch) ------------ */
 int nhip_timing_enable(nhip_ctx *ctx, int on);

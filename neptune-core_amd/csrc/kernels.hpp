@@ -89,10 +89,52 @@ struct MsApplyDev {
     uint32_t* out_np;            // 2 x n_jobs
     uint64_t* out_n;             // 3 x n_jobs: aocl.num_leafs, swbf_inactive.num_leafs, n_active
     uint32_t* out_active;
+    // k_ms_apply<true> only (nhip_ms_update_batch)
+    uint64_t* carry;             // n_jobs x 2 x 64 digests: the left edge of the AOCL append, of the SWBF append
+    uint64_t* carry_mask;        // n_jobs x 2: the heights kept there
 };
 hipError_t launch_ms_chunk_auth_jobs(const MsApplyDev& a, size_t entries, hipStream_t st);
 hipError_t launch_ms_records_jobs(const MsApplyDev& a, size_t n_records, hipStream_t st);
-hipError_t launch_ms_apply(const MsApplyDev& a, size_t n_jobs, hipStream_t st);
+hipError_t launch_ms_apply(const MsApplyDev& a, size_t n_jobs, hipStream_t st, bool keep_nodes = false);
+
+// ---- witnesses across a block (ms_update_kernels.hip); every pointer a device pointer
+// The witnesses of all jobs, the plan's shape (MsUpdatePlan, ms_update_plan.hpp) and the outputs.  The kernels run
+// behind k_ms_apply<true> and read its MsApplyDev: the jobs, their statuses, the group table and the kept nodes.
+struct MsUpdateDev {
+    const uint64_t* minimum;          // witnesses x 2
+    const uint32_t* distances;        // witnesses x 45
+    const uint64_t* aocl_leaf_index;  // ~0: no AOCL part
+    const uint64_t* aocl_leaf;        // witnesses x 5
+    const uint64_t* aocl_path_off;
+    const uint64_t* aocl_path;
+    const uint64_t* entry_off;        // the input dictionaries
+    const uint64_t* chunk_index;
+    const uint64_t* path_off;
+    const uint64_t* path;
+    const uint64_t* rel_off;
+    const uint32_t* rel;
+    const uint8_t* auth;              // per input entry, from k_ms_chunk_auth_jobs
+    const uint32_t* wit_job;          // per witness
+    // the plan
+    const uint64_t* o_aocl_path_off;  // witnesses + 1
+    const uint64_t* o_entry_off;      // witnesses + 1
+    const uint64_t* o_key;            // per output entry
+    const uint64_t* o_path_off;
+    const uint64_t* o_rel_off;
+    const uint32_t* o_ent_wit;
+    const uint64_t* o_ent_src;
+    // outputs
+    uint8_t* status;                  // per witness
+    uint8_t* err;                     // per witness: a digest was found nowhere
+    uint64_t* o_aocl_path;
+    uint64_t* o_chunk_index;
+    uint64_t* o_path;
+    uint32_t* o_rel;
+};
+hipError_t launch_ms_wit_admit(const MsApplyDev& a, const MsUpdateDev& u, size_t witnesses, hipStream_t st);
+hipError_t launch_ms_wit_paths(const MsApplyDev& a, const MsUpdateDev& u, size_t witnesses, size_t entries, hipStream_t st);
+hipError_t launch_ms_wit_chunks(const MsApplyDev& a, const MsUpdateDev& u, size_t entries, hipStream_t st);
+hipError_t launch_ms_wit_seal(const MsUpdateDev& u, size_t witnesses, hipStream_t st);
 
 // ---- packed removal records (ms_unpack_kernels.hip); every pointer a device pointer
 // The program of MsUnpackPlan (ms_unpack_plan.hpp) and the buffers it runs over.

@@ -36,80 +36,17 @@ namespace nhip {
 
 namespace {
 
-using u128 = unsigned __int128;
-static constexpr uint64_t MSA_NONE = ~0ull;
-
-__device__ __forceinline__ uint64_t sat_dec(uint64_t x) { return x ? x - 1 : 0; }
-
-// hash_pair on canonical digests
-__device__ __forceinline__ void dig_hp(const uint64_t* l, const uint64_t* r, uint64_t* out,
-                                       const uint8_t* __restrict__ lut) {
-    uint64_t s[16];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        s[k] = to_mont(l[k]);
-        s[5 + k] = to_mont(r[k]);
-    }
-    tip5_hash_pair_digest(s, lut);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) out[k] = from_mont(s[k]);
-}
-
-// the job's indices in the host's order: slot s -> (index, record in job)
-struct JobIndices {
-    const uint64_t* mn;    // the job's first record
-    const uint32_t* dist;
-    const uint32_t* perm;
-    __device__ __forceinline__ u128 at(uint64_t s, uint32_t* rec = nullptr) const {
-        const uint32_t p = perm[s];
-        const uint32_t r = p / MSK_NUM_TRIALS;
-        if (rec) *rec = r;
-        return (((u128)mn[2 * (size_t)r + 1] << 64) | mn[2 * (size_t)r]) + dist[p];
-    }
-    // first slot in [lo, hi) whose index is >= v
-    __device__ __forceinline__ uint64_t lower_bound(uint64_t lo, uint64_t hi, u128 v) const {
-        while (lo < hi) {
-            const uint64_t mid = lo + (hi - lo) / 2;
-            if (at(mid) < v) lo = mid + 1;
-            else hi = mid;
-        }
-        return lo;
-    }
-};
-
-// first position in the sorted a[0 .. n) with a[pos] >= x
-__device__ __forceinline__ uint64_t lb_u32(const uint32_t* a, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if ((uint64_t)a[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// first group in [0, n) whose chunk index (aux[2 g + 1]) shifted right by sh is >= key
-__device__ __forceinline__ uint64_t lb_group(const uint64_t* aux, uint64_t n, uint32_t sh, uint64_t key) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if ((aux[2 * mid + 1] >> sh) < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// index of the peak of height h in the peak list of an MMR of n leaves (bit h of n set)
-__device__ __forceinline__ uint32_t peak_of_height(uint64_t n, uint32_t h) {
-    return h >= 63 ? 0u : (uint32_t)__popcll(n >> (h + 1));
-}
-
 // Appends cnt leaves (canonical digests, global) to the MMR (peaks_in, n); n + cnt does not wrap.
 // scratch: room for cnt digests.  out: 64 digests; returns the number of peaks.  Called by the whole
 // workgroup; orph: 2 x 64 x 5 words of LDS.  Ends behind a barrier.
+// REC (nhip_ms_update_batch): the nodes along the left edge are kept as well, the one of height
+// h (it holds position n and leaves on both sides of it) in carry[5 h ..] with bit h of *carry_mask set; the
+// nodes wholly inside the range stay in scratch, level after level from height 1 on, as they always did.
+template <bool REC>
 __device__ uint32_t block_mmr_append(const uint64_t* peaks_in, uint64_t n, const uint64_t* leaves, uint64_t cnt,
                                      uint64_t* scratch, uint64_t* out, uint64_t (*orph)[64][5],
-                                     const uint8_t* __restrict__ lut) {
+                                     const uint8_t* __restrict__ lut, uint64_t* carry = nullptr,
+                                     uint64_t* carry_mask = nullptr) {
     const uint32_t tid = threadIdx.x;
     const uint64_t n1 = n + cnt;
     {
@@ -139,6 +76,7 @@ __device__ uint32_t block_mmr_append(const uint64_t* peaks_in, uint64_t n, const
     if (tid == 0) {
         uint64_t c[5] = {0, 0, 0, 0, 0};
         bool have_c = false, done = false;
+        uint64_t kept = 0;
         for (uint32_t L = 0; L < 64 && !done; ++L) {
             const bool a_bit = (n >> L) & 1;
             const uint64_t low = L ? (n & ((1ull << L) - 1)) : 0;
@@ -170,8 +108,14 @@ __device__ uint32_t block_mmr_append(const uint64_t* peaks_in, uint64_t n, const
 #pragma unroll
                 for (int k = 0; k < 5; ++k) c[k] = t[k];
                 have_c = true;
+                if (REC && L + 1 < 64) {
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) carry[5 * (size_t)(L + 1) + k] = t[k];
+                    kept |= 1ull << (L + 1);
+                }
             }
         }
+        if (REC) *carry_mask = kept;
         uint32_t w = 0;
         for (int h = 63; h >= 0; --h) {
             if (!((n1 >> h) & 1)) continue;
@@ -219,6 +163,10 @@ __global__ void __launch_bounds__(256) k_ms_records_jobs(MsApplyDev a, size_t n)
     }
 }
 
+// REC: the nodes a witness of the job may need after the block are kept: both appends' left
+// edges in a.carry, and every level of the leaf mutation (level L of group g at d_mut + 5 (L n_grp + g)) where
+// the plain form swaps two buffers.  Nothing else differs, and the plain form compiles to what it was.
+template <bool REC>
 __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
     __shared__ Tip5Lds t5;
     __shared__ uint64_t sh_orph[2][64][5];
@@ -319,8 +267,9 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
             const uint32_t* grp = a.grp + jb.grp_off + j;  // n_grp + 1 starts per job
             const uint64_t n_grp = jb.n_grp;
 
-            np_aocl = block_mmr_append(a.peaks + 5 * jb.aocl_peaks, n0, a.additions + 5 * jb.add_off, k, d_aocl, o_aocl,
-                                       sh_orph, t5.lut);
+            np_aocl = block_mmr_append<REC>(a.peaks + 5 * jb.aocl_peaks, n0, a.additions + 5 * jb.add_off, k, d_aocl,
+                                            o_aocl, sh_orph, t5.lut, REC ? a.carry + j * 2 * 64 * 5 : nullptr,
+                                            REC ? a.carry_mask + 2 * j : nullptr);
 
             // the groups' chunk indices; touched: [0, T), new chunks: [T, T1), still active: [T1, n_grp)
             for (uint64_t g = tid; g < n_grp; g += blockDim.x) aux[2 * g + 1] = (uint64_t)(ix.at(grp[g]) >> MSK_CHUNK_BITS);
@@ -411,9 +360,14 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
                     }
                 }
                 __syncthreads();
-                uint64_t* t = cur;
-                cur = nxt;
-                nxt = t;
+                if (REC) {
+                    cur = nxt;
+                    nxt += 5 * n_grp;
+                } else {
+                    uint64_t* t = cur;
+                    cur = nxt;
+                    nxt = t;
+                }
             }
             // the peaks of swbf_inactive after the mutation
             if (tid < jb.swbf_np) {
@@ -435,7 +389,9 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
                 for (int q = 0; q < 5; ++q) sh_peaks[tid][q] = src[q];
             }
             __syncthreads();
-            np_swbf = block_mmr_append(&sh_peaks[0][0], b0, d_new, slides, d_new + 5 * slides, o_swbf, sh_orph, t5.lut);
+            np_swbf = block_mmr_append<REC>(&sh_peaks[0][0], b0, d_new, slides, d_new + 5 * slides, o_swbf, sh_orph, t5.lut,
+                                            REC ? a.carry + (j * 2 + 1) * 64 * 5 : nullptr,
+                                            REC ? a.carry_mask + 2 * j + 1 : nullptr);
 
             // the window after: the old indices past the slid chunks, shifted down, merged with the inserted ones
             const bool all_slid = slides >= MSK_WINDOW_CHUNKS;
@@ -510,9 +466,11 @@ hipError_t launch_ms_records_jobs(const MsApplyDev& a, size_t n_records, hipStre
     return hipGetLastError();
 }
 
-hipError_t launch_ms_apply(const MsApplyDev& a, size_t n_jobs, hipStream_t st) {
+hipError_t launch_ms_apply(const MsApplyDev& a, size_t n_jobs, hipStream_t st, bool keep_nodes) {
     if (n_jobs == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_apply, dim3((unsigned)(n_jobs > 65536 ? 65536 : n_jobs)), dim3(256), 0, st, a, n_jobs);
+    const dim3 grid((unsigned)(n_jobs > 65536 ? 65536 : n_jobs));
+    if (keep_nodes) hipLaunchKernelGGL(k_ms_apply<true>, grid, dim3(256), 0, st, a, n_jobs);
+    else hipLaunchKernelGGL(k_ms_apply<false>, grid, dim3(256), 0, st, a, n_jobs);
     return hipGetLastError();
 }
 

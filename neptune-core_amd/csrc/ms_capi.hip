@@ -10,6 +10,7 @@
 #include "ctx.hpp"
 #include "kernels.hpp"
 #include "ms_shape.hpp"
+#include "ms_update_plan.hpp"
 
 using nhip::Stage;
 
@@ -65,14 +66,25 @@ struct UnpackProgram {
     }
 };
 
+// nhip_ms_update_batch's witnesses inside apply_batch's call: inputs that passed ms_update_ok, the
+// host plan, and an output that passed ms_updated_check for a fill
+struct UpdateArgs {
+    const nhip_ms_update_in* wit;
+    const nhip::MsUpdateCounts* counts;
+    const nhip::MsUpdatePlan* plan;
+    nhip_ms_updated* out;
+};
+
 // nhip_ms_apply_batch's body (in and out passed ms_apply_ok, n_jobs != 0).  With `packed`, in->chunks is the plan's
-// unpacked shape without paths, and the paths are filled on the device from the packed dictionaries first.
+// unpacked shape without paths, and the paths are filled on the device from the packed dictionaries first.  With
+// `upd`, k_ms_apply keeps its nodes and the witness kernels run behind it.
 int apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out, const nhip::MsApplyCounts& cnt,
-                const nhip::MsUnpackPlan* plan, const nhip_ms_chunks* packed, const nhip::MsChunkCounts* packed_counts) {
+                const nhip::MsUnpackPlan* plan, const nhip_ms_chunks* packed, const nhip::MsChunkCounts* packed_counts,
+                const UpdateArgs* upd = nullptr) {
     const size_t n = in->n_jobs;
     const size_t R = (size_t)cnt.records, E = (size_t)cnt.chunks.entries;
     nhip::MsApplyOrder o;
-    nhip::ms_apply_order(in, out, cnt, &o);
+    nhip::ms_apply_order(in, out, cnt, &o, upd != nullptr);
     const nhip_ms_chunks none{};  // no record: the dictionaries may be absent
     static const nhip::MsUnpackPlan no_plan;
     UnpackProgram prog(plan ? *plan : no_plan);
@@ -106,6 +118,45 @@ int apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out,
     st.tmp(a.out_np, n, 2);
     st.tmp(a.out_n, n, 3);  // aocl.num_leafs, swbf_inactive.num_leafs, n_active
     st.tmp(a.out_active, (size_t)o.win_total);
+    nhip::MsUpdateDev ud{};
+    nhip::MsRecordsDev wrec{};  // the witnesses' dictionaries as k_ms_chunk_auth_jobs reads a record's
+    const uint32_t* d_in_ent_wit = nullptr;
+    uint8_t* d_wauth = nullptr;
+    size_t W = 0, WE = 0, WA = 0, OE = 0, OPD = 0, ORW = 0;
+    if (upd) {
+        const nhip_ms_update_in& wi = *upd->wit;
+        const nhip::MsUpdatePlan& up = *upd->plan;
+        W = (size_t)upd->counts->witnesses;
+        WE = (size_t)upd->counts->chunks.entries;
+        WA = (size_t)up.aocl_path_off[W];
+        OE = up.chunk_index.size();
+        OPD = (size_t)up.path_off[OE];
+        ORW = (size_t)up.rel_off[OE];
+        st.tmp(a.carry, 2 * n, 64 * 5);
+        st.tmp(a.carry_mask, 2 * n);
+        st.in(ud.minimum, wi.minimum, W, 2);
+        st.in(ud.distances, wi.distances, W, 45);
+        st.in(ud.aocl_leaf_index, wi.aocl_leaf_index, W);
+        st.in(ud.aocl_leaf, wi.aocl_leaf, W, 5);
+        st.in(ud.aocl_path_off, wi.aocl_path_off, W ? W + 1 : 0);
+        st.in(ud.aocl_path, wi.aocl_path, (size_t)upd->counts->aocl_digests, 5);
+        stage_chunks(st, W ? *wi.chunks : none, W, upd->counts->chunks, wrec, ud.path_off, ud.path);
+        st.in(ud.wit_job, up.wit_job.data(), W);
+        st.in(d_in_ent_wit, up.in_ent_wit.data(), WE);
+        st.in(ud.o_aocl_path_off, up.aocl_path_off.data(), W + 1);
+        st.in(ud.o_entry_off, up.entry_off.data(), W + 1);
+        st.in(ud.o_key, up.chunk_index.data(), OE);
+        st.in(ud.o_path_off, up.path_off.data(), OE + 1);
+        st.in(ud.o_rel_off, up.rel_off.data(), OE + 1);
+        st.in(ud.o_ent_wit, up.ent_wit.data(), OE);
+        st.in(ud.o_ent_src, up.ent_src.data(), OE);
+        st.tmp(d_wauth, WE);
+        st.tmp(ud.status, W, 2);  // per witness: status, error byte
+        st.tmp(ud.o_aocl_path, WA, 5);
+        st.tmp(ud.o_chunk_index, OE);
+        st.tmp(ud.o_path, OPD, 5);
+        st.tmp(ud.o_rel, ORW);
+    }
     if (st.commit()) return st.finish();
     a.rec.verdict = a.rec.valid + R;
     a.rec.status = a.rec.valid + 2 * R;
@@ -117,7 +168,34 @@ int apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out,
     }
     st.launch([&] { return nhip::launch_ms_chunk_auth_jobs(a, E, c->stream); });
     st.launch([&] { return nhip::launch_ms_records_jobs(a, R, c->stream); });
-    st.launch([&] { return nhip::launch_ms_apply(a, n, c->stream); });
+    st.launch([&] { return nhip::launch_ms_apply(a, n, c->stream, upd != nullptr); });
+    std::vector<uint8_t> wstatus(W);
+    if (upd) {
+        ud.entry_off = wrec.entry_off;
+        ud.chunk_index = wrec.chunk_index;
+        ud.rel_off = wrec.rel_off;
+        ud.rel = wrec.rel;
+        ud.auth = d_wauth;
+        ud.err = ud.status + W;
+        // the witnesses' entries against their jobs' swbf_inactive: the same kernel, entry -> witness -> job
+        nhip::MsApplyDev wa = a;
+        wa.rec = wrec;
+        wa.rec.auth = d_wauth;
+        wa.path_off = ud.path_off;
+        wa.path = ud.path;
+        wa.entry_rec = d_in_ent_wit;
+        wa.rec_job = ud.wit_job;
+        st.launch([&] { return nhip::launch_ms_chunk_auth_jobs(wa, WE, c->stream); });
+        st.launch([&] { return nhip::launch_ms_wit_admit(a, ud, W, c->stream); });
+        st.launch([&] { return nhip::launch_ms_wit_paths(a, ud, W, OE, c->stream); });
+        st.launch([&] { return nhip::launch_ms_wit_chunks(a, ud, OE, c->stream); });
+        st.launch([&] { return nhip::launch_ms_wit_seal(ud, W, c->stream); });
+        st.out(wstatus.data(), ud.status, W);
+        st.out(upd->out->aocl_path, ud.o_aocl_path, 5 * WA);
+        st.out(upd->out->chunk_index, ud.o_chunk_index, OE);
+        st.out(upd->out->path, ud.o_path, 5 * OPD);
+        st.out(upd->out->rel, ud.o_rel, ORW);
+    }
     // into temporaries first: the outputs stay untouched unless the whole call succeeds
     std::vector<uint8_t> vs(2 * n);
     std::vector<uint64_t> bad(n);
@@ -138,6 +216,11 @@ int apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_out* out,
         std::copy(vs.begin(), vs.begin() + n, out->verdict);
         std::copy(vs.begin() + n, vs.end(), out->status);
         std::copy(bad.begin(), bad.end(), out->bad_record);
+        if (upd) {
+            // the offset arrays and totals from the plan; chunk_index is the device's (zero for a rejected witness)
+            nhip::ms_updated_write(*upd->plan, false, upd->out);
+            std::copy(wstatus.begin(), wstatus.end(), upd->out->status);
+        }
     }
     return rc;
 }
@@ -293,6 +376,30 @@ int nhip_ms_apply_batch(nhip_ctx* c, const nhip_ms_apply_in* in, nhip_ms_apply_o
     if (in->n_jobs == 0) return NHIP_OK;
     try {
         return apply_batch(c, in, out, cnt, nullptr, nullptr, nullptr);
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// MsMembershipProof / RemovalRecord batch_update_from_addition and batch_update_from_remove over whole blocks, as the
+// end state: nhip_ms_apply_batch with its nodes kept, then k_ms_chunk_auth_jobs over the witnesses'
+// dictionaries, k_ms_wit_admit, k_ms_wit_paths, k_ms_wit_chunks, k_ms_wit_seal.  The host lays out shapes only.
+int nhip_ms_update_batch(nhip_ctx* c, const nhip_ms_apply_in* block, nhip_ms_apply_out* block_out,
+                         const nhip_ms_update_in* wit, nhip_ms_updated* out) {
+    nhip::MsApplyCounts cnt;
+    nhip::MsUpdateCounts wc;
+    if (!c || !out || nhip::ms_apply_ok(block, block_out, &cnt) || nhip::ms_update_ok(block, wit, &wc)) return NHIP_ERR_ARG;
+    try {
+        nhip::MsUpdatePlan plan;
+        int rc = nhip::ms_update_plan(block, wit, wc, &plan);
+        if (rc != NHIP_OK) return rc;
+        if ((rc = nhip::ms_updated_check(plan, true, out)) != NHIP_OK) return rc;
+        if (nhip::ms_updated_is_count_pass(out) || block->n_jobs == 0) {
+            nhip::ms_updated_write(plan, true, out);
+            return NHIP_OK;
+        }
+        const UpdateArgs upd{wit, &wc, &plan, out};
+        return apply_batch(c, block, block_out, cnt, nullptr, nullptr, nullptr, &upd);
     } catch (const std::bad_alloc&) {
         return NHIP_ERR_OOM;
     }

@@ -167,4 +167,73 @@ __device__ __forceinline__ void ms_record_decide(const MsRecordsDev& r, size_t i
     }
 }
 
+// ---- shared by k_ms_apply (ms_apply_kernels.hip) and the witness kernels (ms_update_kernels.hip)
+using u128 = unsigned __int128;
+static constexpr uint64_t MSA_NONE = ~0ull;
+
+__device__ __forceinline__ uint64_t sat_dec(uint64_t x) { return x ? x - 1 : 0; }
+
+// hash_pair on canonical digests
+__device__ __forceinline__ void dig_hp(const uint64_t* l, const uint64_t* r, uint64_t* out,
+                                       const uint8_t* __restrict__ lut) {
+    uint64_t s[16];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        s[k] = to_mont(l[k]);
+        s[5 + k] = to_mont(r[k]);
+    }
+    tip5_hash_pair_digest(s, lut);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) out[k] = from_mont(s[k]);
+}
+
+// the job's indices in the host's order: slot s -> (index, record in job)
+struct JobIndices {
+    const uint64_t* mn;    // the job's first record
+    const uint32_t* dist;
+    const uint32_t* perm;
+    __device__ __forceinline__ u128 at(uint64_t s, uint32_t* rec = nullptr) const {
+        const uint32_t p = perm[s];
+        const uint32_t r = p / MSK_NUM_TRIALS;
+        if (rec) *rec = r;
+        return (((u128)mn[2 * (size_t)r + 1] << 64) | mn[2 * (size_t)r]) + dist[p];
+    }
+    // first slot in [lo, hi) whose index is >= v
+    __device__ __forceinline__ uint64_t lower_bound(uint64_t lo, uint64_t hi, u128 v) const {
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (at(mid) < v) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo;
+    }
+};
+
+// first position in the sorted a[0 .. n) with a[pos] >= x
+__device__ __forceinline__ uint64_t lb_u32(const uint32_t* a, uint64_t n, uint64_t x) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if ((uint64_t)a[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// first group in [0, n) whose chunk index (aux[2 g + 1]) shifted right by sh is >= key
+__device__ __forceinline__ uint64_t lb_group(const uint64_t* aux, uint64_t n, uint32_t sh, uint64_t key) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if ((aux[2 * mid + 1] >> sh) < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// index of the peak of height h in the peak list of an MMR of n leaves (bit h of n set)
+__device__ __forceinline__ uint32_t peak_of_height(uint64_t n, uint32_t h) {
+    return h >= 63 ? 0u : (uint32_t)__popcll(n >> (h + 1));
+}
+
 }  // namespace nhip

@@ -50,16 +50,15 @@ int ms_chunks_ok(const nhip_ms_chunks* chunks, size_t n, MsChunkCounts* counts) 
     return NHIP_OK;
 }
 
-int ms_apply_ok(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, MsApplyCounts* counts) {
-    if (!in || !out) return NHIP_ERR_ARG;
+int ms_apply_in_ok(const nhip_ms_apply_in* in, MsApplyCounts* counts) {
+    if (!in) return NHIP_ERR_ARG;
     MsApplyCounts c;
     const size_t n = in->n_jobs;
     if (n == 0) {
         if (counts) *counts = c;
         return NHIP_OK;
     }
-    if (n > (size_t)UINT32_MAX || !in->msa_before || !out->verdict || !out->status || !out->bad_record)
-        return NHIP_ERR_ARG;
+    if (n > (size_t)UINT32_MAX || !in->msa_before) return NHIP_ERR_ARG;
     if (ms_csr_ok(in->add_off, n, 5 * sizeof(uint64_t), &c.additions)) return NHIP_ERR_ARG;
     if (c.additions && !in->additions) return NHIP_ERR_ARG;
     if (ms_csr_ok(in->rec_off, n, 45 * sizeof(uint32_t), &c.records)) return NHIP_ERR_ARG;
@@ -67,6 +66,25 @@ int ms_apply_ok(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, MsAppl
         if (!in->minimum || !in->distances) return NHIP_ERR_ARG;
         if (ms_chunks_ok(in->chunks, (size_t)c.records, &c.chunks)) return NHIP_ERR_ARG;
     }
+    for (size_t j = 0; j < n; ++j) {
+        if (ms_msa_ok(&in->msa_before[j])) return NHIP_ERR_ARG;
+        if (in->msa_expected && ms_msa_ok(&in->msa_expected[j])) return NHIP_ERR_ARG;
+        if (in->rec_off[j + 1] - in->rec_off[j] > (uint64_t)UINT32_MAX / 45) return NHIP_ERR_ARG;
+    }
+    if (counts) *counts = c;
+    return NHIP_OK;
+}
+
+int ms_apply_ok(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, MsApplyCounts* counts) {
+    if (!in || !out) return NHIP_ERR_ARG;
+    MsApplyCounts c;
+    if (ms_apply_in_ok(in, &c)) return NHIP_ERR_ARG;
+    const size_t n = in->n_jobs;
+    if (n == 0) {
+        if (counts) *counts = c;
+        return NHIP_OK;
+    }
+    if (!out->verdict || !out->status || !out->bad_record) return NHIP_ERR_ARG;
     const int given = (out->aocl_peaks != nullptr) + (out->aocl_n_peaks != nullptr) + (out->aocl_num_leafs != nullptr) +
                       (out->swbf_peaks != nullptr) + (out->swbf_n_peaks != nullptr) + (out->swbf_num_leafs != nullptr) +
                       (out->active_off != nullptr) + (out->n_active != nullptr);
@@ -79,10 +97,7 @@ int ms_apply_ok(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, MsAppl
         return NHIP_ERR_ARG;
     }
     for (size_t j = 0; j < n; ++j) {
-        if (ms_msa_ok(&in->msa_before[j])) return NHIP_ERR_ARG;
-        if (in->msa_expected && ms_msa_ok(&in->msa_expected[j])) return NHIP_ERR_ARG;
         const uint64_t m = in->rec_off[j + 1] - in->rec_off[j];
-        if (m > (uint64_t)UINT32_MAX / 45) return NHIP_ERR_ARG;
         const uint64_t need = in->msa_before[j].n_active + 45 * m;  // n_active <= SIZE_MAX / 8: no wrap
         if (c.accumulators && out->active_off[j + 1] - out->active_off[j] < need) return NHIP_ERR_ARG;
     }
@@ -109,7 +124,7 @@ std::vector<uint64_t> ms_interleave15(const uint64_t* items, const uint64_t* sen
 }
 
 void ms_apply_order(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, const MsApplyCounts& cnt,
-                    MsApplyOrder* o) {
+                    MsApplyOrder* o, bool keep_nodes) {
     using u128 = unsigned __int128;
     const size_t n = in->n_jobs, R = (size_t)cnt.records, E = (size_t)cnt.chunks.entries;
     *o = MsApplyOrder{};
@@ -184,7 +199,10 @@ void ms_apply_order(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, co
         const uint64_t slides =
             n1 < jb.aocl_n ? 0 : (n1 ? n1 - 1 : 0) / 8 - (jb.aocl_n ? jb.aocl_n - 1 : 0) / 8;  // <= k / 8 + 1
         jb.dig_off = o->dig_total;
-        o->dig_total += (jb.k + 1) + (2 * slides + 1) + 2 * jb.n_grp;
+        uint64_t levels = keep_nodes ? 1 : 2;  // the leaf mutation's two buffers, or one per level 0 .. ilog2(b0) + 1
+        if (keep_nodes)
+            for (uint64_t b = (jb.aocl_n ? jb.aocl_n - 1 : 0) / 8; b; b >>= 1) ++levels;
+        o->dig_total += (jb.k + 1) + (2 * slides + 1) + levels * jb.n_grp;
         jb.win_off = cnt.accumulators ? out->active_off[j] : o->win_total;
         jb.win_cap = cnt.accumulators ? out->active_off[j + 1] - out->active_off[j] : jb.n_active + 45 * jb.m;
         o->win_total += jb.win_cap;

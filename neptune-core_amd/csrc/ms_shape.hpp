@@ -43,6 +43,8 @@ struct MsApplyCounts {
 // ms_chunks_ok, at most (2^32 - 1) / 45 records in a job, the accumulator outputs all null or all present,
 // and every job's window capacity >= n_active + 45 records.  Hashes nothing, decides nothing.
 int ms_apply_ok(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, MsApplyCounts* counts);
+// its input half alone (nhip_ms_update_plan has no nhip_ms_apply_out); counts->accumulators stays false
+int ms_apply_in_ok(const nhip_ms_apply_in* in, MsApplyCounts* counts);
 
 // ---- staged order: inputs that passed the checks above; hashes nothing, decides nothing;
 // may throw std::bad_alloc
@@ -64,7 +66,7 @@ struct MsApplyJob {
     uint64_t add_off, k;              // addition records
     uint64_t rec_off, m;              // removal records (idx_perm: 45 rec_off; rec_perm: rec_off)
     uint64_t grp_off, n_grp;          // groups before this job; its n_grp + 1 starts are grp[grp_off + job ..]
-    uint64_t dig_off;                 // digest scratch: k + 1, 2 slides + 1, 2 n_grp
+    uint64_t dig_off;                 // digest scratch: k + 1, 2 slides + 1, 2 n_grp (keep_nodes: (ilog2(b0) + 2) n_grp)
     uint64_t win_off, win_cap;        // the window after in out_active
     uint64_t exp_aocl_n, exp_swbf_n, exp_aocl_peaks, exp_swbf_peaks, exp_act_off, exp_n_active;
     uint32_t aocl_np, swbf_np, exp_aocl_np, exp_swbf_np;
@@ -78,7 +80,8 @@ struct MsApplyOrder {
     std::vector<uint32_t> active, exp_active, rec_job, entry_rec, idx_perm, grp, rec_perm;
     uint64_t dig_total = 0, grp_total = 0, win_total = 0;
 };
+// keep_nodes: room for every level of the leaf mutation (k_ms_apply<true>, nhip_ms_update_batch)
 void ms_apply_order(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, const MsApplyCounts& cnt,
-                    MsApplyOrder* o);
+                    MsApplyOrder* o, bool keep_nodes = false);
 
 }  // namespace nhip

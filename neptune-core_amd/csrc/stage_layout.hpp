@@ -10,7 +10,7 @@
 namespace nhip {
 
 static constexpr size_t STAGE_ALIGN = 256;
-static constexpr unsigned STAGE_MAX_BUFS = 40;  // nhip_ms_apply_batch_packed declares 35
+static constexpr unsigned STAGE_MAX_BUFS = 64;  // nhip_ms_update_batch declares 58
 
 struct StageLayout {
     size_t off[STAGE_MAX_BUFS], bytes[STAGE_MAX_BUFS];

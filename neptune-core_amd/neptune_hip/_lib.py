@@ -167,6 +167,23 @@ class MsUnpacked(ctypes.Structure):
                 ("path_digests", ctypes.c_size_t), ("rel_words", ctypes.c_size_t)]
 
 
+class MsUpdateIn(ctypes.Structure):
+    """nhip_ms_update_in: the witnesses of the jobs of one nhip_ms_update_batch call (CSR over the jobs)."""
+    _fields_ = [("wit_off", ctypes.c_void_p), ("minimum", ctypes.c_void_p), ("distances", ctypes.c_void_p),
+                ("aocl_leaf_index", ctypes.c_void_p), ("aocl_leaf", ctypes.c_void_p), ("aocl_path_off", ctypes.c_void_p),
+                ("aocl_path", ctypes.c_void_p), ("chunks", ctypes.POINTER(MsChunks))]
+
+
+class MsUpdated(ctypes.Structure):
+    """nhip_ms_updated: per-witness statuses, the AOCL paths and the dictionaries after the block."""
+    _fields_ = [("status", ctypes.c_void_p), ("aocl_path_off", ctypes.c_void_p), ("aocl_path", ctypes.c_void_p),
+                ("entry_off", ctypes.c_void_p), ("chunk_index", ctypes.c_void_p), ("path_off", ctypes.c_void_p),
+                ("path", ctypes.c_void_p), ("rel_off", ctypes.c_void_p), ("rel", ctypes.c_void_p),
+                ("aocl_cap", ctypes.c_size_t), ("entries_cap", ctypes.c_size_t), ("path_cap", ctypes.c_size_t),
+                ("rel_cap", ctypes.c_size_t), ("aocl_digests", ctypes.c_size_t), ("entries", ctypes.c_size_t),
+                ("path_digests", ctypes.c_size_t), ("rel_words", ctypes.c_size_t)]
+
+
 _pp = ctypes.POINTER(ctypes.c_void_p)
 
 # (name, argtypes) for every symbol of include/neptune_hip.h
@@ -249,6 +266,10 @@ SIGNATURES = {
     "nhip_ms_unpack_batch": ([_vp, _vp, _sz, _vp, _vp, ctypes.POINTER(MsChunks), ctypes.POINTER(MsUnpacked)],
                              ctypes.c_int),
     "nhip_ms_apply_batch_packed": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut)], ctypes.c_int),
+    "nhip_ms_update_plan": ([ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsUpdateIn), ctypes.POINTER(MsUpdated)],
+                            ctypes.c_int),
+    "nhip_ms_update_batch": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut), ctypes.POINTER(MsUpdateIn),
+                              ctypes.POINTER(MsUpdated)], ctypes.c_int),
     "nhip_proof_decodes": ([_vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof)],
                            ctypes.c_int),
     "nhip_verify_batch": ([_vp, _vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof),

@@ -19,6 +19,12 @@ consensus step after "the proof verifies", batched.
   is its host half (statuses and shapes, no GPU), and `apply_update_batch_packed(ctx, jobs, expected=None)` is
   rules 2.a-2.e in one call over packed lists.
 
+* `update_witnesses_batch(ctx, jobs)` — `MsMembershipProof::batch_update_from_addition` / `batch_update_from_remove`
+  (ms_membership_proof.rs:76-270,417-468) and `RemovalRecord::batch_update_from_addition` / `batch_update_from_remove`
+  (removal_record.rs:49-200) over whole blocks, as the end state; `update_plan_batch(jobs)` is its
+  host half (the shapes, no GPU), `update_membership_proofs` and `update_removal_records` are the wallet's and the
+  mempool's calls (state/wallet/wallet_state.rs:1375,1481; state/mod.rs:1537,1557,2507,2522).
+
 The types mirror the reference's over numpy; every verdict is the device's.  Where the reference
 would panic or truncate (an index past the active window, or >= 2^76) the record is rejected with
 `OUT_OF_RANGE`.
@@ -27,7 +33,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass, field
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -50,9 +56,13 @@ UNPACK_STATUS_NAMES = ("UNPACK_PAYLOAD_TOO_BIG", "UNPACK_INCONSISTENT_LENGTH", "
                        "UNPACK_INCONSISTENT_CHUNKS", "UNPACK_STRUCTURE_COUNT", "UNPACK_STRUCTURE_LENGTH", "UNPACK_PANIC")
 
 
+JOB_REJECTED, UPDATE_INTERNAL = 20, 21  # update_witnesses_batch only (a witness's status)
+UPDATE_STATUS_NAMES = ("JOB_REJECTED", "UPDATE_INTERNAL")
+
+
 def status_name(status: int) -> str:
-    """The name of any NHIP_MS_* status, the rule 2.a ones included."""
-    return (STATUS_NAMES + UNPACK_STATUS_NAMES)[status]
+    """The name of any NHIP_MS_* status, the rule 2.a and the witness ones included."""
+    return (STATUS_NAMES + UNPACK_STATUS_NAMES + UPDATE_STATUS_NAMES)[status]
 
 
 def _digests(x, n=None) -> np.ndarray:
@@ -313,9 +323,13 @@ def apply_update_batch(ctx, jobs, expected=None, _packed=False):
         return []
     pa = PackedApply(jobs, expected)
     check(pa.call(ctx, _packed), "nhip_ms_apply_batch_packed" if _packed else "nhip_ms_apply_batch")
+    return _apply_results(pa)
+
+
+def _apply_results(pa):
     a = pa.arrays
     out = []
-    for j in range(n):
+    for j in range(pa.n):
         after = None
         status = int(a["status"][j])
         if status in (OK, UPDATE_MISMATCH):
@@ -392,3 +406,140 @@ def unpack_removal_records_batch(ctx, jobs):
         recs = [RemovalRecord(pl.index_sets[r], dictionaries[r]) for r in range(lo, hi)]
         out.append((int(status[j]), recs if int(status[j]) == OK else None))
     return out
+
+
+# ---------------------------------------------------------------- witnesses across a block
+@dataclass
+class Witness:
+    """What `nhip_ms_update_batch` brings up to date: an index set and a chunk dictionary, and for a membership
+    proof its AOCL part (leaf index, the addition record's canonical commitment, authentication path).
+    `aocl_leaf_index` None: a removal record."""
+    absolute_indices: AbsoluteIndexSet
+    target_chunks: List[Tuple[int, Sequence[Sequence[int]], Chunk]] = field(default_factory=list)
+    aocl_leaf_index: Optional[int] = None
+    aocl_leaf: Sequence[int] = ()
+    auth_path_aocl: Sequence[Sequence[int]] = ()
+
+
+class PackedUpdate:
+    """The arguments of `nhip_ms_update_plan` / `nhip_ms_update_batch` over numpy arrays.  `jobs`: `(msa_before,
+    MutatorSetUpdate, witnesses)` triples.  `apply` is the block half (`PackedApply`), `win` the witnesses' struct,
+    `out` the output arrays once `plan` or `run` has sized them."""
+
+    def __init__(self, jobs, expected=None):
+        self.n = len(jobs)
+        self.apply = PackedApply([(m, u) for m, u, _ in jobs], expected)
+        wits = self.witnesses = [w for _, _, ws in jobs for w in ws]
+        W = self.n_witnesses = len(wits)
+        self.wit_off = _csr([len(ws) for _, _, ws in jobs])
+        self.minimum, self.distances = _index_arrays(wits)
+        self.leaf_index = np.asarray([2 ** 64 - 1 if w.aocl_leaf_index is None else int(w.aocl_leaf_index) for w in wits],
+                                     dtype=np.uint64)
+        self.leaf = np.zeros((W, 5), dtype=np.uint64)
+        for i, w in enumerate(wits):
+            if w.aocl_leaf_index is not None:
+                self.leaf[i] = np.asarray([int(x) for x in w.aocl_leaf], dtype=np.uint64)
+        self.aocl_path_off, self.aocl_path = pack_paths([w.auth_path_aocl for w in wits])
+        self.packed = pack_chunks(wits)
+        self.chunks = self.packed._c()
+        self.win = _lib.MsUpdateIn(self.wit_off.ctypes.data, _ptr(self.minimum), _ptr(self.distances),
+                                   _ptr(self.leaf_index), _ptr(self.leaf), self.aocl_path_off.ctypes.data,
+                                   _ptr(self.aocl_path), ctypes.pointer(self.chunks))
+        self.out = None
+        self.cout = None
+
+    def _call(self, lib, handle):
+        if handle is None:
+            return lib.nhip_ms_update_plan(ctypes.byref(self.apply.cin), ctypes.byref(self.win), ctypes.byref(self.cout))
+        return lib.nhip_ms_update_batch(handle, ctypes.byref(self.apply.cin), ctypes.byref(self.apply.cout),
+                                        ctypes.byref(self.win), ctypes.byref(self.cout))
+
+    def run(self, lib, handle=None) -> int:
+        """Both calls of the two-call pattern; with no `handle` the host plan alone (statuses, digests and chunk
+        words stay zero).  Returns the second call's code; `out` holds the arrays."""
+        W = self.n_witnesses
+        self.cout = _lib.MsUpdated()
+        rc = lib.nhip_ms_update_plan(ctypes.byref(self.apply.cin), ctypes.byref(self.win), ctypes.byref(self.cout))
+        if rc != _lib.NHIP_OK:
+            return rc
+        A, E, PD, RW = (int(getattr(self.cout, f)) for f in ("aocl_digests", "entries", "path_digests", "rel_words"))
+        z = lambda dtype, *shape: np.zeros(shape, dtype=dtype)  # noqa: E731
+        o = self.out = dict(status=z(np.uint8, W), aocl_path_off=z(np.uint64, W + 1), aocl_path=z(np.uint64, A, 5),
+                            entry_off=z(np.uint64, W + 1), chunk_index=z(np.uint64, E), path_off=z(np.uint64, E + 1),
+                            path=z(np.uint64, PD, 5), rel_off=z(np.uint64, E + 1), rel=z(np.uint32, RW))
+        # a zero-size array still gets an address: only the count pass has null array pointers
+        self._pad = {f: (a if a.size else np.zeros(1, dtype=a.dtype)) for f, a in o.items()}
+        self.cout = _lib.MsUpdated(*(self._pad[f].ctypes.data for f, _ in _lib.MsUpdated._fields_[:9]), A, E, PD, RW)
+        return self._call(lib, handle)
+
+    def dictionaries(self) -> PackedChunks:
+        o = self.out
+        return PackedChunks(o["entry_off"], o["chunk_index"], o["path_off"], o["path"], o["rel_off"], o["rel"])
+
+
+def update_plan_batch(jobs):
+    """The host half of `update_witnesses_batch` (no GPU): the output arrays as `nhip_ms_update_plan` lays them out
+    (`aocl_path_off`, `entry_off`, `chunk_index`, `path_off`, `rel_off`; the rest zero)."""
+    pu = PackedUpdate(jobs)
+    check(pu.run(_lib.load()), "nhip_ms_update_plan")
+    return pu.out
+
+
+def update_witnesses_batch(ctx, jobs, expected=None):
+    """`jobs`: `(MutatorSetAccumulator before, MutatorSetUpdate, [Witness])` triples, independent of each other.  Per
+    job `(verdict, status, bad_record, msa_after, witnesses)` with the first four as `apply_update_batch` gives them
+    and `witnesses` a list of `(status, Witness after the block or None)`: a witness is brought up to date only when
+    its job's status is OK and it passes admission against `msa_before` (the order of `nhip_ms_update_batch`)."""
+    if len(jobs) == 0:
+        return []
+    pu = PackedUpdate(jobs, expected)
+    check(pu.run(ctx.lib, ctx.handle), "nhip_ms_update_batch")
+    block = _apply_results(pu.apply)
+    o = pu.out
+    dictionaries = unpack_chunks(pu.dictionaries())
+    out = []
+    for j in range(pu.n):
+        ws = []
+        for i in range(int(pu.wit_off[j]), int(pu.wit_off[j + 1])):
+            st, old = int(o["status"][i]), pu.witnesses[i]
+            if st != OK:
+                ws.append((st, None))
+                continue
+            path = [tuple(int(x) for x in d) for d in o["aocl_path"][int(o["aocl_path_off"][i]):int(o["aocl_path_off"][i + 1])]]
+            ws.append((st, Witness(old.absolute_indices, dictionaries[i], old.aocl_leaf_index, old.aocl_leaf, path)))
+        out.append(block[j] + (ws,))
+    return out
+
+
+def update_membership_proofs(ctx, msa_before: MutatorSetAccumulator, update: MutatorSetUpdate, items,
+                             proofs: Sequence[MsMembershipProof]):
+    """The wallet's step after a block (wallet_state.rs:1375,1481): every monitored UTXO's membership proof brought
+    up to the accumulator after `update`.  The index sets (`AbsoluteIndexSet::compute`) and the AOCL leaves
+    (`hash_pair(hash_pair(item, sender_randomness), hash_pair(receiver_preimage, 0))`) are derived on the device.
+    `(job status, msa_after or None, [(status, MsMembershipProof or None)])`."""
+    if len(items) != len(proofs):
+        raise ValueError("one membership proof per item")
+    wits = []
+    if len(proofs):
+        it = _digests(items, len(proofs))
+        sr = _digests([p.sender_randomness for p in proofs], len(proofs))
+        rp = _digests([p.receiver_preimage for p in proofs], len(proofs))
+        sets = AbsoluteIndexSet.compute_batch(ctx, it, sr, rp, [int(p.aocl_leaf_index) for p in proofs])
+        leaves = ctx.hash_pair(ctx.hash_pair(it, sr), ctx.hash_pair(rp, np.zeros_like(rp)))
+        wits = [Witness(s, list(p.target_chunks), int(p.aocl_leaf_index), [int(x) for x in leaf], list(p.auth_path_aocl))
+                for s, p, leaf in zip(sets, proofs, leaves)]
+    _, status, _, after, ws = update_witnesses_batch(ctx, [(msa_before, update, wits)])[0]
+    out = [(st, None if w is None else MsMembershipProof(p.sender_randomness, p.receiver_preimage, w.auth_path_aocl,
+                                                         p.aocl_leaf_index, w.target_chunks))
+           for (st, w), p in zip(ws, proofs)]
+    return status, after, out
+
+
+def update_removal_records(ctx, msa_before: MutatorSetAccumulator, update: MutatorSetUpdate,
+                           records: Sequence[RemovalRecord]):
+    """The mempool's step after a block (state/mod.rs:1537,1557,2507,2522): every pending transaction's removal records
+    brought up to the accumulator after `update`.  `(job status, msa_after or None, [(status, RemovalRecord or
+    None)])`."""
+    wits = [Witness(r.absolute_indices, list(r.target_chunks)) for r in records]
+    _, status, _, after, ws = update_witnesses_batch(ctx, [(msa_before, update, wits)])[0]
+    return status, after, [(st, None if w is None else RemovalRecord(w.absolute_indices, w.target_chunks)) for st, w in ws]

@@ -267,6 +267,49 @@ pub const NHIP_MS_UNPACK_INCONSISTENT_CHUNKS: u8 = 16;
 pub const NHIP_MS_UNPACK_STRUCTURE_COUNT: u8 = 17;
 pub const NHIP_MS_UNPACK_STRUCTURE_LENGTH: u8 = 18;
 pub const NHIP_MS_UNPACK_PANIC: u8 = 19;
+/// `nhip_ms_update_batch` only: the witness's job did not end `NHIP_MS_OK`.
+pub const NHIP_MS_JOB_REJECTED: u8 = 20;
+/// `nhip_ms_update_batch` only: a digest the witness needs was found nowhere it can come from.
+pub const NHIP_MS_UPDATE_INTERNAL: u8 = 21;
+
+/// The witnesses (membership proofs and removal records) of the jobs of one `nhip_ms_update_batch` call, CSR over
+/// the jobs; `aocl_leaf_index == u64::MAX` marks a removal record.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_ms_update_in {
+    pub wit_off: *const u64,
+    pub minimum: *const u64,
+    pub distances: *const u32,
+    pub aocl_leaf_index: *const u64,
+    pub aocl_leaf: *const u64,
+    pub aocl_path_off: *const u64,
+    pub aocl_path: *const u64,
+    pub chunks: *const nhip_ms_chunks,
+}
+
+/// Per-witness statuses, AOCL paths and dictionaries after the block (two-call sizing: every array pointer but
+/// `status` null writes the totals only).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_ms_updated {
+    pub status: *mut u8,
+    pub aocl_path_off: *mut u64,
+    pub aocl_path: *mut u64,
+    pub entry_off: *mut u64,
+    pub chunk_index: *mut u64,
+    pub path_off: *mut u64,
+    pub path: *mut u64,
+    pub rel_off: *mut u64,
+    pub rel: *mut u32,
+    pub aocl_cap: usize,
+    pub entries_cap: usize,
+    pub path_cap: usize,
+    pub rel_cap: usize,
+    pub aocl_digests: usize,
+    pub entries: usize,
+    pub path_digests: usize,
+    pub rel_words: usize,
+}
 
 /// Statuses and the unpacked dictionaries of `nhip_ms_unpack_plan` / `nhip_ms_unpack_batch` (two-call sizing:
 /// every array pointer but `status` and `num_leafs_aocl` null writes the totals only).
@@ -531,6 +574,10 @@ extern "C" {
                                 out: *mut nhip_ms_unpacked) -> c_int;
     pub fn nhip_ms_apply_batch_packed(ctx: *mut nhip_ctx, input: *const nhip_ms_apply_in,
                                       out: *mut nhip_ms_apply_out) -> c_int;
+    pub fn nhip_ms_update_plan(block: *const nhip_ms_apply_in, wit: *const nhip_ms_update_in,
+                               out: *mut nhip_ms_updated) -> c_int;
+    pub fn nhip_ms_update_batch(ctx: *mut nhip_ctx, block: *const nhip_ms_apply_in, block_out: *mut nhip_ms_apply_out,
+                                wit: *const nhip_ms_update_in, out: *mut nhip_ms_updated) -> c_int;
     pub fn nhip_timing_enable(ctx: *mut nhip_ctx, on: c_int) -> c_int;
     pub fn nhip_timing_read(ctx: *mut nhip_ctx, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
 }
