@@ -35,14 +35,19 @@ struct MmrDev {
     uint32_t n_peaks;
     uint64_t num_leafs;
 };
+// The chunk dictionaries of n owners (records or witnesses), flattened, on the device (nhip_ms_chunks on the host):
+// owner i has the entries entry_off[i] .. entry_off[i + 1], in dictionary order.
+struct MsChunksDev {
+    const uint64_t *entry_off, *chunk_index;  // n + 1; per entry
+    const uint64_t *path_off, *path;          // entries + 1, in digests; MMR authentication paths, leaf sibling first
+    const uint64_t* rel_off;                  // entries + 1, in u32
+    const uint32_t* rel;                      // Chunk::relative_indices
+};
 struct MsRecordsDev {
     const uint64_t* minimum;    // n x 2 (u128, little-endian)
     const uint32_t* distances;  // n x 45
-    const uint64_t* entry_off;  // n + 1
-    const uint64_t* chunk_index;
-    const uint64_t* rel_off;
-    const uint32_t* rel;
-    const uint8_t* auth;         // per entry, from k_ms_chunk_auth
+    MsChunksDev ch;
+    const uint8_t* auth;         // per entry, from k_ms_chunk_auth / k_ms_chunk_auth_jobs
     const uint8_t* aocl_member;  // per record, from k_ms_aocl_leaf: verify; nullptr: validate / can_remove
     const uint32_t* active;      // the active window's indices, sorted ascending
     uint64_t n_active;
@@ -57,9 +62,7 @@ hipError_t launch_mmr_verify(const MmrDev& mmr, const uint64_t* d_leaf_index, co
 hipError_t launch_ms_aocl_leaf(const MmrDev& aocl, const uint64_t* d_digests, const uint64_t* d_leaf_index,
                                const uint64_t* d_path_off, const uint64_t* d_path, size_t n, uint8_t* d_member,
                                hipStream_t st);
-hipError_t launch_ms_chunk_auth(const MmrDev& swbf, const uint64_t* d_chunk_index, const uint64_t* d_path_off,
-                                const uint64_t* d_path, const uint64_t* d_rel_off, const uint32_t* d_rel,
-                                size_t entries, uint8_t* d_auth, hipStream_t st);
+hipError_t launch_ms_chunk_auth(const MmrDev& swbf, const MsChunksDev& ch, size_t entries, uint8_t* d_auth, hipStream_t st);
 hipError_t launch_ms_records(const MsRecordsDev& r, size_t n, hipStream_t st);
 
 // ---- batched mutator-set updates (ms_apply_kernels.hip); every pointer a device pointer
@@ -70,10 +73,7 @@ struct MsApplyDev {
     const uint32_t* active;      // every job's active window, sorted ascending
     const uint64_t* additions;   // canonical commitments
     MsRecordsDev rec;            // the records of all jobs, and k_ms_records_jobs' outputs
-    const uint64_t* path_off;
-    const uint64_t* path;
     const uint32_t* rec_job;     // per record
-    const uint32_t* entry_rec;   // per dictionary entry
     uint8_t* index_set;          // 45 per record (ms_record_decide)
     const uint32_t* idx_perm;    // per job: its 45 m index slots (record-in-job x 45 + t) sorted by (index, record)
     const uint32_t* grp;         // per job: the starts of the runs of one chunk index in that order, then 45 m
@@ -93,7 +93,15 @@ struct MsApplyDev {
     uint64_t* carry;             // n_jobs x 2 x 64 digests: the left edge of the AOCL append, of the SWBF append
     uint64_t* carry_mask;        // n_jobs x 2: the heights kept there
 };
-hipError_t launch_ms_chunk_auth_jobs(const MsApplyDev& a, size_t entries, hipStream_t st);
+// k_ms_chunk_auth_jobs: the job looked up entry -> owner -> job; the owners are the block's records or its witnesses
+struct MsChunkAuthJobsDev {
+    const MsApplyJob* jobs;
+    const uint64_t* peaks;                    // MsApplyDev::peaks
+    MsChunksDev ch;
+    const uint32_t *entry_owner, *owner_job;  // per entry, per owner
+    uint8_t* auth;                            // per entry: 1 = the chunk is in the job's swbf_inactive at chunk_index
+};
+hipError_t launch_ms_chunk_auth_jobs(const MsChunkAuthJobsDev& c, size_t entries, hipStream_t st);
 hipError_t launch_ms_records_jobs(const MsApplyDev& a, size_t n_records, hipStream_t st);
 hipError_t launch_ms_apply(const MsApplyDev& a, size_t n_jobs, hipStream_t st, bool keep_nodes = false);
 
@@ -107,12 +115,7 @@ struct MsUpdateDev {
     const uint64_t* aocl_leaf;        // witnesses x 5
     const uint64_t* aocl_path_off;
     const uint64_t* aocl_path;
-    const uint64_t* entry_off;        // the input dictionaries
-    const uint64_t* chunk_index;
-    const uint64_t* path_off;
-    const uint64_t* path;
-    const uint64_t* rel_off;
-    const uint32_t* rel;
+    MsChunksDev ch;                   // the input dictionaries
     const uint8_t* auth;              // per input entry, from k_ms_chunk_auth_jobs
     const uint32_t* wit_job;          // per witness
     // the plan

@@ -3,12 +3,13 @@
 // for many independent jobs, each (msa_before, addition records, removal records, optional expected
 // accumulator).  The end state is computed directly, not record by record.
 //
-//  k_ms_chunk_auth_jobs : k_ms_chunk_auth with the entry's job looked up (entry -> record -> job): the
-//                         same chunk sponge and MMR climb against that job's swbf_inactive.
+//  k_ms_chunk_auth_jobs : k_ms_chunk_auth with the entry's job looked up (MsChunkAuthJobsDev: entry -> owner -> job,
+//                         the owners the block's records or nhip_ms_update_batch's witnesses): the same
+//                         ms_chunk_auth_entry against that job's swbf_inactive.
 //  k_ms_records_jobs    : k_ms_records with the record's job looked up (ms_record_decide), which also
 //                         leaves one byte per index: set in msa_before or not.
 //  k_ms_apply           : one 256-thread workgroup per job, every phase strided over the job's items with
-//                         barriers between them; scratch in global memory, so a job of any size runs.
+//                         barriers between them; scratch in global memory (MsJobScratch), so a job of any size runs.
 //                           1  consistency of msa_before
 //                           2  the first record k_ms_records_jobs rejected (2.b)
 //                           3  equal neighbours in the host's order of the records (2.c)
@@ -135,21 +136,13 @@ __device__ uint32_t block_mmr_append(const uint64_t* peaks_in, uint64_t n, const
 
 }  // namespace
 
-__global__ void __launch_bounds__(256) k_ms_chunk_auth_jobs(MsApplyDev a, size_t entries) {
+__global__ void __launch_bounds__(256) k_ms_chunk_auth_jobs(MsChunkAuthJobsDev c, size_t entries) {
     __shared__ Tip5Lds t5;
     tip5_lds_init(t5);
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < entries;
-         e += (size_t)gridDim.x * blockDim.x) {
-        const MsApplyJob& jb = a.jobs[a.rec_job[a.entry_rec[e]]];
-        const MmrDev swbf{a.peaks + 5 * jb.swbf_peaks, jb.swbf_np, jb.swbf_n};
-        const uint64_t rbeg = a.rec.rel_off[e];
-        const uint64_t cnt = a.rec.rel_off[e + 1] - rbeg;
-        const uint32_t* __restrict__ idx = a.rec.rel + rbeg;
-        uint64_t run[5];
-        ms_chunk_sponge(cnt, [&](uint64_t w) { return idx[w]; }, run, t5.lut);
-        const uint64_t beg = a.path_off[e];
-        const_cast<uint8_t*>(a.rec.auth)[e] =
-            mmr_climb(run, a.rec.chunk_index[e], swbf, a.path + 5 * beg, a.path_off[e + 1] - beg, t5.lut) ? 1 : 0;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < entries; e += (size_t)gridDim.x * blockDim.x) {
+        const MsApplyJob& jb = c.jobs[c.owner_job[c.entry_owner[e]]];
+        const MmrDev swbf{c.peaks + 5 * jb.swbf_peaks, jb.swbf_np, jb.swbf_n};
+        c.auth[e] = ms_chunk_auth_entry(c.ch, e, swbf, t5.lut) ? 1 : 0;
     }
 }
 
@@ -164,7 +157,7 @@ __global__ void __launch_bounds__(256) k_ms_records_jobs(MsApplyDev a, size_t n)
 }
 
 // REC: the nodes a witness of the job may need after the block are kept: both appends' left
-// edges in a.carry, and every level of the leaf mutation (level L of group g at d_mut + 5 (L n_grp + g)) where
+// edges in a.carry, and every level of the leaf mutation (level L of group g at MsJobScratch::mut_node(n_grp, L, g)) where
 // the plain form swaps two buffers.  Nothing else differs, and the plain form compiles to what it was.
 template <bool REC>
 __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
@@ -177,8 +170,8 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
     const uint32_t tid = threadIdx.x;
     for (size_t j = blockIdx.x; j < n_jobs; j += gridDim.x) {  // workgroup-uniform
         const MsApplyJob jb = a.jobs[j];
-        const uint64_t n0 = jb.aocl_n, k = jb.k, n1 = n0 + k, m = jb.m;
-        const uint64_t b0 = sat_dec(n0) / MSK_BATCH_SIZE, b1 = sat_dec(n1) / MSK_BATCH_SIZE;
+        const MsJobScratch s(jb.aocl_n, jb.k);
+        const uint64_t n0 = s.n0, k = jb.k, n1 = s.n1, b0 = s.b0, b1 = s.b1, m = jb.m;
         const uint64_t n_idx = MSK_NUM_TRIALS * m;
         const JobIndices ix{a.rec.minimum + 2 * jb.rec_off, a.rec.distances + MSK_NUM_TRIALS * jb.rec_off,
                             a.idx_perm + MSK_NUM_TRIALS * jb.rec_off};
@@ -188,7 +181,7 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
 
         // 1. consistency
         if ((uint32_t)__popcll(n0) != jb.aocl_np || (uint32_t)__popcll(jb.swbf_n) != jb.swbf_np || jb.swbf_n != b0 ||
-            n1 < n0)
+            s.wrapped())
             status = NHIP_MS_INCONSISTENT;
 
         // 2. rule 2.b: the first record k_ms_records_jobs rejected
@@ -259,15 +252,14 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
         uint32_t np_aocl = 0, np_swbf = 0;
         if (status == NHIP_MS_OK) {
             // 5. the accumulator after
-            uint64_t* d_aocl = a.dig + 5 * jb.dig_off;
-            const uint64_t slides = b1 - b0;
-            uint64_t* d_new = d_aocl + 5 * (k + 1);      // the new chunks' digests, then their levels
-            uint64_t* d_mut = d_new + 5 * (2 * slides + 1);  // 2 x n_grp: the touched leaves, level by level
+            uint64_t* dig = a.dig + 5 * jb.dig_off;  // the job's scratch: MsJobScratch (ms_shape.hpp)
+            uint64_t* d_new = dig + 5 * s.fresh();  // the new chunks' digests, then their levels
+            uint64_t* d_mut = dig + 5 * s.mut();    // the touched leaves, level by level
             uint64_t* aux = a.aux + 2 * jb.grp_off;
             const uint32_t* grp = a.grp + jb.grp_off + j;  // n_grp + 1 starts per job
             const uint64_t n_grp = jb.n_grp;
 
-            np_aocl = block_mmr_append<REC>(a.peaks + 5 * jb.aocl_peaks, n0, a.additions + 5 * jb.add_off, k, d_aocl,
+            np_aocl = block_mmr_append<REC>(a.peaks + 5 * jb.aocl_peaks, n0, a.additions + 5 * jb.add_off, k, dig + 5 * s.aocl(),
                                             o_aocl, sh_orph, t5.lut, REC ? a.carry + j * 2 * 64 * 5 : nullptr,
                                             REC ? a.carry_mask + 2 * j : nullptr);
 
@@ -278,7 +270,7 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
 
             // Tip5::hash of every touched chunk (old content: its dictionary entry) and of every new chunk
             // (old content: its part of the window), merged with the inserted indices as they are absorbed
-            for (uint64_t i = tid; i < T + slides; i += blockDim.x) {
+            for (uint64_t i = tid; i < T + s.slides; i += blockDim.x) {
                 const uint32_t* old = nullptr;
                 uint64_t n_old = 0, s0 = 0, s1 = 0;
                 uint32_t bias = 0;
@@ -289,14 +281,14 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
                     s1 = grp[i + 1];
                     (void)ix.at(s0, &rec);
                     const uint64_t ci = aux[2 * i + 1], grec = jb.rec_off + rec;
-                    uint64_t e = a.rec.entry_off[grec];
-                    const uint64_t eend = a.rec.entry_off[grec + 1];
-                    while (e < eend && a.rec.chunk_index[e] != ci) ++e;
+                    uint64_t e = a.rec.ch.entry_off[grec];
+                    const uint64_t eend = a.rec.ch.entry_off[grec + 1];
+                    while (e < eend && a.rec.ch.chunk_index[e] != ci) ++e;
                     if (e == eend) e = MSA_NONE;  // not reached: the record validated
                     aux[2 * i] = e;
                     if (e != MSA_NONE) {
-                        old = a.rec.rel + a.rec.rel_off[e];
-                        n_old = a.rec.rel_off[e + 1] - a.rec.rel_off[e];
+                        old = a.rec.ch.rel + a.rec.ch.rel_off[e];
+                        n_old = a.rec.ch.rel_off[e + 1] - a.rec.ch.rel_off[e];
                     }
                     dst = d_mut + 5 * i;
                 } else {
@@ -339,7 +331,7 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
             // leaf mutation, level-synchronous: a touched leaf's sibling at a level is another touched
             // leaf's node (the new value) or the digest of its own path
             uint64_t* cur = d_mut;
-            uint64_t* nxt = d_mut + 5 * n_grp;
+            uint64_t* nxt = dig + 5 * s.mut_node(n_grp, 1, 0);
             const uint32_t max_h = b0 ? 63u - (uint32_t)__clzll((long long)b0) : 0u;
             for (uint32_t L = 0; L < max_h && T; ++L) {
                 for (uint64_t g = tid; g < T; g += blockDim.x) {
@@ -351,7 +343,7 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
                         const uint64_t e = aux[2 * g];
                         const uint64_t* sd = cur + 5 * g;  // e == MSA_NONE is not reached
                         if (x < T && (aux[2 * x + 1] >> L) == sib) sd = cur + 5 * x;
-                        else if (e != MSA_NONE) sd = a.path + 5 * (a.path_off[e] + L);  // path_len == h: authenticated
+                        else if (e != MSA_NONE) sd = a.rec.ch.path + 5 * (a.rec.ch.path_off[e] + L);  // path_len == h: authenticated
                         if (node & 1) dig_hp(sd, cur + 5 * g, nxt + 5 * g, t5.lut);
                         else dig_hp(cur + 5 * g, sd, nxt + 5 * g, t5.lut);
                     } else {
@@ -362,7 +354,7 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
                 __syncthreads();
                 if (REC) {
                     cur = nxt;
-                    nxt += 5 * n_grp;
+                    nxt += 5 * s.mut_stride(n_grp);
                 } else {
                     uint64_t* t = cur;
                     cur = nxt;
@@ -389,13 +381,13 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
                 for (int q = 0; q < 5; ++q) sh_peaks[tid][q] = src[q];
             }
             __syncthreads();
-            np_swbf = block_mmr_append<REC>(&sh_peaks[0][0], b0, d_new, slides, d_new + 5 * slides, o_swbf, sh_orph, t5.lut,
+            np_swbf = block_mmr_append<REC>(&sh_peaks[0][0], b0, d_new, s.slides, dig + 5 * s.fresh_levels(), o_swbf, sh_orph, t5.lut,
                                             REC ? a.carry + (j * 2 + 1) * 64 * 5 : nullptr,
                                             REC ? a.carry_mask + 2 * j + 1 : nullptr);
 
             // the window after: the old indices past the slid chunks, shifted down, merged with the inserted ones
-            const bool all_slid = slides >= MSK_WINDOW_CHUNKS;
-            const uint64_t shift = all_slid ? 0 : slides << MSK_CHUNK_BITS;
+            const bool all_slid = s.slides >= MSK_WINDOW_CHUNKS;
+            const uint64_t shift = all_slid ? 0 : s.slides << MSK_CHUNK_BITS;
             const uint64_t la = all_slid ? jb.n_active : lb_u32(act, jb.n_active, shift);
             const uint64_t kept = jb.n_active - la;
             const uint64_t s_ins = n_grp ? grp[T1] : 0;  // grp[n_grp] = n_idx
@@ -449,21 +441,12 @@ __global__ void __launch_bounds__(256) k_ms_apply(MsApplyDev a, size_t n_jobs) {
     }
 }
 
-static inline unsigned apply_grid(size_t n) {
-    const size_t g = (n + 255) / 256;
-    return (unsigned)(g > 16384 ? 16384 : g);  // grid-stride beyond 16k workgroups
-}
-
-hipError_t launch_ms_chunk_auth_jobs(const MsApplyDev& a, size_t entries, hipStream_t st) {
-    if (entries == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_chunk_auth_jobs, dim3(apply_grid(entries)), dim3(256), 0, st, a, entries);
-    return hipGetLastError();
+hipError_t launch_ms_chunk_auth_jobs(const MsChunkAuthJobsDev& c, size_t entries, hipStream_t st) {
+    return ms_launch(k_ms_chunk_auth_jobs, entries, st, c, entries);
 }
 
 hipError_t launch_ms_records_jobs(const MsApplyDev& a, size_t n_records, hipStream_t st) {
-    if (n_records == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_records_jobs, dim3(apply_grid(64 * n_records)), dim3(256), 0, st, a, n_records);  // a wave per record
-    return hipGetLastError();
+    return ms_launch(k_ms_records_jobs, 64 * n_records, st, a, n_records);  // a wave per record
 }
 
 hipError_t launch_ms_apply(const MsApplyDev& a, size_t n_jobs, hipStream_t st, bool keep_nodes) {

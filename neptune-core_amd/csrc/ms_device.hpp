@@ -1,6 +1,6 @@
 // Device functions shared by the mutator-set kernels (ms_kernels.hip: one accumulator per launch;
-// ms_apply_kernels.hip: one accumulator per job): the MMR climb, the chunk sponge and the per-record
-// validate / can_remove decision.  DESIGN.md §6c, §6d.
+// ms_apply_kernels.hip: one accumulator per job): the MMR climb, the chunk sponge, the authentication of one
+// dictionary entry, the per-record validate / can_remove decision, the lane-per-item launch.  DESIGN.md §6c, §6d.
 #pragma once
 #include "../../include/neptune_hip.h"
 #include "kernels.hpp"
@@ -9,7 +9,7 @@
 namespace nhip {
 
 static constexpr uint32_t MSK_CHUNK_BITS = 12;                     // CHUNK_SIZE = 2^12 (shared.rs:13)
-static constexpr uint32_t MSK_BATCH_SIZE = 8;                      // BATCH_SIZE (shared.rs:14)
+static constexpr uint32_t MSK_BATCH_SIZE = MsJobScratch::BATCH_SIZE;  // BATCH_SIZE (shared.rs:14)
 static constexpr uint32_t MSK_WINDOW_CHUNKS = 1u << (20 - 12);     // WINDOW_SIZE / CHUNK_SIZE
 static constexpr uint32_t MSK_NUM_TRIALS = 45;                     // NUM_TRIALS (shared.rs:15)
 
@@ -81,6 +81,27 @@ __device__ __forceinline__ void ms_chunk_sponge(uint64_t cnt, Word&& word, uint6
     for (int k = 0; k < 5; ++k) run[k] = s[k];
 }
 
+// Entry e of the dictionaries ch against swbf: Tip5::hash(chunk), then the MMR climb at leaf index chunk_index[e]
+// (removal_record.rs:237-243, mutator_set_accumulator.rs:309-316).  k_ms_chunk_auth and k_ms_chunk_auth_jobs.
+__device__ __forceinline__ bool ms_chunk_auth_entry(const MsChunksDev& ch, size_t e, const MmrDev& swbf,
+                                                    const uint8_t* __restrict__ lut) {
+    const uint64_t rbeg = ch.rel_off[e], cnt = ch.rel_off[e + 1] - rbeg;
+    const uint32_t* __restrict__ idx = ch.rel + rbeg;
+    uint64_t run[5];
+    ms_chunk_sponge(cnt, [&](uint64_t w) { return idx[w]; }, run, lut);
+    const uint64_t beg = ch.path_off[e];
+    return mmr_climb(run, ch.chunk_index[e], swbf, ch.path + 5 * beg, ch.path_off[e + 1] - beg, lut);
+}
+
+// kernel(args...) in 256-thread workgroups over `lanes` lanes' worth of items; nothing to do is no launch
+template <class Kernel, class... Args>
+hipError_t ms_launch(Kernel kernel, size_t lanes, hipStream_t st, Args... args) {
+    if (lanes == 0) return hipSuccess;
+    const size_t g = (lanes + 255) / 256;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, st, args...);  // then grid-stride
+    return hipGetLastError();
+}
+
 // active: sorted ascending
 __device__ __forceinline__ bool active_contains(const uint32_t* __restrict__ active, uint64_t n_active, uint32_t x) {
     uint64_t lo = 0, hi = n_active;
@@ -105,12 +126,12 @@ __device__ __forceinline__ void ms_record_decide(const MsRecordsDev& r, size_t i
                                                  uint64_t aocl_num_leafs, uint8_t* __restrict__ index_set) {
     using u128 = unsigned __int128;
     // get_batch_index (util_types/mutator_set.rs:74-76) and the active window's first index
-    const uint64_t batch = (aocl_num_leafs ? aocl_num_leafs - 1 : 0) / MSK_BATCH_SIZE;
+    const uint64_t batch = MsJobScratch::batch_index(aocl_num_leafs);
     const u128 start = (u128)batch << MSK_CHUNK_BITS;
     const u128 chunk_max = (u128)batch + (MSK_WINDOW_CHUNKS - 1);
     const u128 mn = ((u128)r.minimum[2 * i + 1] << 64) | r.minimum[2 * i];
     const uint32_t* __restrict__ dist = r.distances + (size_t)MSK_NUM_TRIALS * i;
-    const uint64_t ebeg = r.entry_off[i], eend = r.entry_off[i + 1];
+    const uint64_t ebeg = r.ch.entry_off[i], eend = r.ch.entry_off[i + 1];
     const bool not_in_aocl = r.aocl_member && r.aocl_member[i] != 1;
     const bool mine = lane < MSK_NUM_TRIALS;
     // AbsoluteIndexSet::to_array (absolute_index_set.rs:125-131); fail closed past the window
@@ -122,14 +143,14 @@ __device__ __forceinline__ void ms_record_decide(const MsRecordsDev& r, size_t i
             const uint64_t ci = (uint64_t)(index >> MSK_CHUNK_BITS);  // <= batch + 255: exact
             if (ci < batch) {
                 uint64_t e = ebeg;  // ChunkDictionary::get: the first entry with the key
-                while (e < eend && r.chunk_index[e] != ci) ++e;
+                while (e < eend && r.ch.chunk_index[e] != ci) ++e;
                 if (e == eend) {
                     absent_chunk = true;
                 } else {
                     if (r.aocl_member && r.auth[e] != 1) bad_path = true;  // verify: the required entries only
                     const uint32_t want = (uint32_t)index & ((1u << MSK_CHUNK_BITS) - 1);
                     bool found = false;
-                    for (uint64_t k = r.rel_off[e]; k < r.rel_off[e + 1]; ++k) found |= r.rel[k] == want;
+                    for (uint64_t k = r.ch.rel_off[e]; k < r.ch.rel_off[e + 1]; ++k) found |= r.ch.rel[k] == want;
                     has_absent = !found;
                 }
             } else {
@@ -140,7 +161,7 @@ __device__ __forceinline__ void ms_record_decide(const MsRecordsDev& r, size_t i
             // validate: every entry authenticated, and no entry whose chunk index is not required
             for (uint64_t e = ebeg + lane; e < eend; e += 64) {
                 if (r.auth[e] != 1) bad_path = true;
-                const uint64_t ce = r.chunk_index[e];
+                const uint64_t ce = r.ch.chunk_index[e];
                 bool required = false;
                 if (ce < batch)
                     for (uint32_t t = 0; t < MSK_NUM_TRIALS; ++t)
@@ -171,7 +192,6 @@ __device__ __forceinline__ void ms_record_decide(const MsRecordsDev& r, size_t i
 using u128 = unsigned __int128;
 static constexpr uint64_t MSA_NONE = ~0ull;
 
-__device__ __forceinline__ uint64_t sat_dec(uint64_t x) { return x ? x - 1 : 0; }
 
 // hash_pair on canonical digests
 __device__ __forceinline__ void dig_hp(const uint64_t* l, const uint64_t* r, uint64_t* out,

@@ -9,10 +9,10 @@
 //  k_ms_aocl_leaf  : MutatorSetAccumulator::verify's AOCL leg (mutator_set_accumulator.rs:257-278):
 //                    leaf = hash_pair(hash_pair(item, sender_randomness), hash_pair(receiver_preimage,
 //                    0^5)), member of the AOCL at aocl_leaf_index.  One lane per item.
-//  k_ms_chunk_auth : one lane per chunk-dictionary entry (chunk_index, MMR path, Chunk):
+//  k_ms_chunk_auth : one lane per chunk-dictionary entry (chunk_index, MMR path, Chunk) of an MsChunksDev:
 //                    Tip5::hash(chunk) = hash_varlen of its BFieldCodec encoding, then the MMR climb
-//                    against swbf_inactive at leaf index chunk_index (removal_record.rs:237-243,
-//                    mutator_set_accumulator.rs:309-316).  One byte per entry.
+//                    against swbf_inactive at leaf index chunk_index (ms_chunk_auth_entry, ms_device.hpp,
+//                    shared with k_ms_chunk_auth_jobs).  One byte per entry.
 //  k_ms_records    : one wave per record (a lane per index), no Tip5: the 45 absolute indices, the entry bytes and the
 //                    active window -> validate / can_remove (removal_record.rs:202-251,
 //                    mutator_set_accumulator.rs:187-222) or verify (mutator_set_accumulator.rs:280-338).
@@ -75,24 +75,12 @@ __global__ void __launch_bounds__(256) k_ms_aocl_leaf(MmrDev aocl, const uint64_
     }
 }
 
-__global__ void __launch_bounds__(256) k_ms_chunk_auth(MmrDev swbf, const uint64_t* __restrict__ chunk_index,
-                                                       const uint64_t* __restrict__ path_off,
-                                                       const uint64_t* __restrict__ path,
-                                                       const uint64_t* __restrict__ rel_off,
-                                                       const uint32_t* __restrict__ rel, size_t entries,
+__global__ void __launch_bounds__(256) k_ms_chunk_auth(MmrDev swbf, MsChunksDev ch, size_t entries,
                                                        uint8_t* __restrict__ auth) {
     __shared__ Tip5Lds t5;
     tip5_lds_init(t5);
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < entries;
-         e += (size_t)gridDim.x * blockDim.x) {
-        const uint64_t rbeg = rel_off[e];
-        const uint64_t cnt = rel_off[e + 1] - rbeg;
-        const uint32_t* __restrict__ idx = rel + rbeg;
-        uint64_t run[5];
-        ms_chunk_sponge(cnt, [&](uint64_t w) { return idx[w]; }, run, t5.lut);
-        const uint64_t beg = path_off[e];
-        auth[e] = mmr_climb(run, chunk_index[e], swbf, path + 5 * beg, path_off[e + 1] - beg, t5.lut) ? 1 : 0;
-    }
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < entries; e += (size_t)gridDim.x * blockDim.x)
+        auth[e] = ms_chunk_auth_entry(ch, e, swbf, t5.lut) ? 1 : 0;
 }
 
 // One 64-lane wave per record: lane t < 45 takes index t, and the lanes share the record's entries in the
@@ -106,42 +94,24 @@ __global__ void __launch_bounds__(256) k_ms_records(MsRecordsDev r, size_t n) {
         ms_record_decide(r, i, lane, r.active, r.n_active, r.aocl_num_leafs, nullptr);
 }
 
-static inline unsigned ms_grid(size_t n) {
-    const size_t g = (n + 255) / 256;
-    return (unsigned)(g > 16384 ? 16384 : g);  // grid-stride beyond 16k workgroups
-}
-
 hipError_t launch_mmr_verify(const MmrDev& mmr, const uint64_t* d_leaf_index, const uint64_t* d_leaves,
                              const uint64_t* d_path_off, const uint64_t* d_path, size_t n, uint8_t* d_verdicts,
                              hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_mmr_verify, dim3(ms_grid(n)), dim3(256), 0, st, mmr, d_leaf_index, d_leaves, d_path_off,
-                       d_path, n, d_verdicts);
-    return hipGetLastError();
+    return ms_launch(k_mmr_verify, n, st, mmr, d_leaf_index, d_leaves, d_path_off, d_path, n, d_verdicts);
 }
 
 hipError_t launch_ms_aocl_leaf(const MmrDev& aocl, const uint64_t* d_digests, const uint64_t* d_leaf_index,
                                const uint64_t* d_path_off, const uint64_t* d_path, size_t n, uint8_t* d_member,
                                hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_aocl_leaf, dim3(ms_grid(n)), dim3(256), 0, st, aocl, d_digests, d_leaf_index, d_path_off,
-                       d_path, n, d_member);
-    return hipGetLastError();
+    return ms_launch(k_ms_aocl_leaf, n, st, aocl, d_digests, d_leaf_index, d_path_off, d_path, n, d_member);
 }
 
-hipError_t launch_ms_chunk_auth(const MmrDev& swbf, const uint64_t* d_chunk_index, const uint64_t* d_path_off,
-                                const uint64_t* d_path, const uint64_t* d_rel_off, const uint32_t* d_rel,
-                                size_t entries, uint8_t* d_auth, hipStream_t st) {
-    if (entries == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_chunk_auth, dim3(ms_grid(entries)), dim3(256), 0, st, swbf, d_chunk_index, d_path_off,
-                       d_path, d_rel_off, d_rel, entries, d_auth);
-    return hipGetLastError();
+hipError_t launch_ms_chunk_auth(const MmrDev& swbf, const MsChunksDev& ch, size_t entries, uint8_t* d_auth, hipStream_t st) {
+    return ms_launch(k_ms_chunk_auth, entries, st, swbf, ch, entries, d_auth);
 }
 
 hipError_t launch_ms_records(const MsRecordsDev& r, size_t n, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_records, dim3(ms_grid(64 * n)), dim3(256), 0, st, r, n);  // a wave per record
-    return hipGetLastError();
+    return ms_launch(k_ms_records, 64 * n, st, r, n);  // a wave per record
 }
 
 }  // namespace nhip

@@ -195,14 +195,8 @@ void ms_apply_order(const nhip_ms_apply_in* in, const nhip_ms_apply_out* out, co
             return std::lexicographical_compare(vals.begin() + 45 * x, vals.begin() + 45 * x + 45,
                                                 vals.begin() + 45 * y, vals.begin() + 45 * y + 45);
         });
-        const uint64_t n1 = jb.aocl_n + jb.k;
-        const uint64_t slides =
-            n1 < jb.aocl_n ? 0 : (n1 ? n1 - 1 : 0) / 8 - (jb.aocl_n ? jb.aocl_n - 1 : 0) / 8;  // <= k / 8 + 1
         jb.dig_off = o->dig_total;
-        uint64_t levels = keep_nodes ? 1 : 2;  // the leaf mutation's two buffers, or one per level 0 .. ilog2(b0) + 1
-        if (keep_nodes)
-            for (uint64_t b = (jb.aocl_n ? jb.aocl_n - 1 : 0) / 8; b; b >>= 1) ++levels;
-        o->dig_total += (jb.k + 1) + (2 * slides + 1) + levels * jb.n_grp;
+        o->dig_total += MsJobScratch(jb.aocl_n, jb.k).total(jb.n_grp, keep_nodes);
         jb.win_off = cnt.accumulators ? out->active_off[j] : o->win_total;
         jb.win_cap = cnt.accumulators ? out->active_off[j + 1] - out->active_off[j] : jb.n_active + 45 * jb.m;
         o->win_total += jb.win_cap;

@@ -3,8 +3,8 @@
 // and the order it stages besides the caller's own arrays.  Every verdict is the
 // device's; the host refuses (NHIP_ERR_ARG) what it could not stage without reading outside the
 // caller's arrays: a null pointer with a non-zero count, an offset array that does not start at 0
-// or decreases, and totals whose byte size leaves size_t.  Host only (no HIP), so that
-// tests/native/ms_shape_check.cpp and ms_apply_shape_check.cpp link it under ASan + UBSan.
+// or decreases, and totals whose byte size leaves size_t.  Plain C++ (no HIP header; MsJobScratch alone is also the
+// kernels'), so that tests/native/ms_shape_check.cpp and ms_apply_shape_check.cpp link it under ASan + UBSan.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -12,6 +12,12 @@
 #include <vector>
 
 #include "../../include/neptune_hip.h"
+
+#ifdef __HIP__
+#define NHIP_MS_HD __host__ __device__ inline
+#else
+#define NHIP_MS_HD inline
+#endif
 
 namespace nhip {
 
@@ -66,11 +72,43 @@ struct MsApplyJob {
     uint64_t add_off, k;              // addition records
     uint64_t rec_off, m;              // removal records (idx_perm: 45 rec_off; rec_perm: rec_off)
     uint64_t grp_off, n_grp;          // groups before this job; its n_grp + 1 starts are grp[grp_off + job ..]
-    uint64_t dig_off;                 // digest scratch: k + 1, 2 slides + 1, 2 n_grp (keep_nodes: (ilog2(b0) + 2) n_grp)
+    uint64_t dig_off;                 // its digest scratch (MsJobScratch below) in the dig pool
     uint64_t win_off, win_cap;        // the window after in out_active
     uint64_t exp_aocl_n, exp_swbf_n, exp_aocl_peaks, exp_swbf_peaks, exp_act_off, exp_n_active;
     uint32_t aocl_np, swbf_np, exp_aocl_np, exp_swbf_np;
 };
+// The bounds of a job and the layout of its digest scratch, in digests from dig_off: one definition for the host,
+// which sizes the pool from it (ms_apply_order), and for k_ms_apply and the witness kernels, which address every
+// node they keep or look up through it.  Three regions, back to back:
+//   aocl  k + 1            block_mmr_append's levels over the addition records, height 1 first
+//   fresh 2 slides + 1     the new chunks' digests, then (at fresh_levels) the levels of the SWBF append over them
+//   mut   levels x n_grp   the leaf mutation, level L of touched chunk g at mut_node(n_grp, L, g): two levels that
+//                          swap, or with keep_nodes one per height 0 .. ilog2(b0) + 1.  n_grp is an argument, not a
+//                          member, so that a kernel loads it only on the path that needs it.
+// n1 = aocl_n + k may wrap.  The host relies on slides = 0 then (no size follows a wrapped count).  The kernels rely
+// on nothing for such a job: k_ms_apply tests wrapped() and answers NHIP_MS_INCONSISTENT before it touches the
+// scratch, and the witness kernels skip a job that did not end NHIP_MS_OK.
+struct MsJobScratch {
+    static constexpr uint32_t BATCH_SIZE = 8;  // shared.rs:14
+    uint64_t n0, n1, b0, b1;  // before and after: aocl.num_leafs, swbf_inactive.num_leafs (get_batch_index)
+    uint64_t slides;          // b1 - b0 <= k / 8 + 1: the chunks that leave the window
+    NHIP_MS_HD MsJobScratch(uint64_t aocl_n, uint64_t k)
+        : n0(aocl_n), n1(aocl_n + k), b0(batch_index(n0)), b1(batch_index(n1)), slides(n1 < n0 ? 0 : b1 - b0) {}
+    static NHIP_MS_HD uint64_t batch_index(uint64_t num_leafs) { return (num_leafs ? num_leafs - 1 : 0) / BATCH_SIZE; }
+    NHIP_MS_HD bool wrapped() const { return n1 < n0; }
+    NHIP_MS_HD uint64_t aocl() const { return 0; }
+    NHIP_MS_HD uint64_t fresh() const { return (n1 - n0) + 1; }
+    NHIP_MS_HD uint64_t fresh_levels() const { return fresh() + slides; }
+    NHIP_MS_HD uint64_t mut() const { return fresh() + 2 * slides + 1; }
+    static NHIP_MS_HD uint64_t mut_stride(uint64_t n_grp) { return n_grp; }  // one level
+    NHIP_MS_HD uint64_t mut_node(uint64_t n_grp, uint64_t L, uint64_t g) const { return mut() + L * mut_stride(n_grp) + g; }
+    NHIP_MS_HD uint64_t total(uint64_t n_grp, bool keep_nodes) const {
+        uint64_t levels = keep_nodes ? 1 : 2;
+        for (uint64_t b = keep_nodes ? b0 : 0; b; b >>= 1) ++levels;
+        return mut() + levels * mut_stride(n_grp);
+    }
+};
+
 // nhip_ms_apply_batch's staged arrays (MsApplyDev says what the kernels read in each): per job a sorted copy of
 // its window, its index slots sorted by (index, slot) and grouped by chunk index, its records sorted by their
 // index arrays (stable), and its offsets into every pool.

@@ -1,13 +1,12 @@
 // Membership proofs and removal records across a block: every witness of a job of
 // nhip_ms_apply_batch brought up to the accumulator after it, as the end state.  The kernels run behind
 // k_ms_chunk_auth_jobs over the witnesses' dictionaries (the job looked up entry -> witness -> job) and behind
-// k_ms_apply<true>, which keeps the nodes it computes:
-//   the AOCL append    heights >= 1 of the nodes wholly among the appended leaves in the job's digest scratch, level
-//                      after level (block_mmr_append's own layout), height 0 being the addition records; the left
-//                      edge (the nodes that hold old and new leaves) in a.carry;
-//   the leaf mutation  level L of touched chunk g at d_mut + 5 (L n_grp + g), found as the kernel itself finds a
-//                      sibling: lb_group over the group table at that height;
-//   the SWBF append    as the AOCL's, over the new chunks' digests.
+// k_ms_apply<true>, which keeps the nodes it computes in the job's digest scratch.  MsJobScratch (ms_shape.hpp) says
+// where: k_ms_apply writes through it and these kernels read through it.  Both appends leave heights >= 1 of the nodes
+// wholly among the appended leaves level after level (block_mmr_append's own layout; height 0 is the addition records
+// or the new chunks' digests) and their left edge (the nodes that hold old and new leaves) in a.carry; the leaf
+// mutation leaves level L of touched chunk g at mut_node, found as the kernel itself finds a sibling: lb_group over
+// the group table at that height.
 // A node is addressed by where it must lie, not searched in a table: a sibling block is wholly new (scratch),
 // holds the old leaf count (carry) or is wholly old, and then it is a touched node, a digest of the witness's own
 // path, or the old peak of exactly that height.  Anything else sets the witness's error byte: never a guess.
@@ -79,23 +78,22 @@ __global__ void __launch_bounds__(256) k_ms_wit_admit(MsApplyDev a, MsUpdateDev 
             continue;
         }
         const MsApplyJob& jb = a.jobs[j];
-        const uint64_t n0 = jb.aocl_n, n1 = n0 + jb.k;  // no wrap: the job is consistent
-        const uint64_t b0 = sat_dec(n0) / MSK_BATCH_SIZE, b1 = sat_dec(n1) / MSK_BATCH_SIZE;
+        const MsJobScratch s(jb.aocl_n, jb.k);  // no wrap: the job is consistent
         const uint64_t l = u.aocl_leaf_index[w];
         bool in_aocl = true;
         if (l != MSA_NONE) {
             const uint64_t pbeg = u.aocl_path_off[w], plen = u.aocl_path_off[w + 1] - pbeg;
             const uint64_t* leaf = u.aocl_leaf + 5 * w;
-            if (l >= n1) {
+            if (l >= s.n1) {
                 in_aocl = false;
-            } else if (l < n0) {
+            } else if (l < s.n0) {
                 uint64_t run[5];
 #pragma unroll
                 for (int q = 0; q < 5; ++q) run[q] = to_mont(leaf[q]);
-                const MmrDev aocl{a.peaks + 5 * jb.aocl_peaks, jb.aocl_np, n0};
+                const MmrDev aocl{a.peaks + 5 * jb.aocl_peaks, jb.aocl_np, s.n0};
                 in_aocl = mmr_climb(run, l, aocl, u.aocl_path + 5 * pbeg, plen, t5.lut);
             } else {  // born in this block
-                const uint64_t* add = a.additions + 5 * (jb.add_off + (l - n0));
+                const uint64_t* add = a.additions + 5 * (jb.add_off + (l - s.n0));
                 in_aocl = plen == 0;
 #pragma unroll
                 for (int q = 0; q < 5; ++q) in_aocl &= leaf[q] == add[q];
@@ -103,8 +101,8 @@ __global__ void __launch_bounds__(256) k_ms_wit_admit(MsApplyDev a, MsUpdateDev 
         }
         const u128 mn = ((u128)u.minimum[2 * w + 1] << 64) | u.minimum[2 * w];
         const uint32_t* __restrict__ dist = u.distances + (size_t)MSK_NUM_TRIALS * w;
-        const uint64_t ebeg = u.entry_off[w], eend = u.entry_off[w + 1];
-        const u128 chunk_max = (u128)b1 + (MSK_WINDOW_CHUNKS - 1);
+        const uint64_t ebeg = u.ch.entry_off[w], eend = u.ch.entry_off[w + 1];
+        const u128 chunk_max = (u128)s.b1 + (MSK_WINDOW_CHUNKS - 1);
         bool out_of_range = false, absent = false, bad_path = false;
         for (uint32_t t = 0; t < MSK_NUM_TRIALS; ++t) {
             const u128 v = mn + dist[t];
@@ -114,8 +112,8 @@ __global__ void __launch_bounds__(256) k_ms_wit_admit(MsApplyDev a, MsUpdateDev 
             // the keys, strictly ascending, are exactly the chunk indices below b0
             uint64_t prev = 0;
             for (uint64_t e = ebeg; e < eend; ++e) {
-                const uint64_t key = u.chunk_index[e];
-                if ((e > ebeg && key <= prev) || key >= b0) absent = true;
+                const uint64_t key = u.ch.chunk_index[e];
+                if ((e > ebeg && key <= prev) || key >= s.b0) absent = true;
                 prev = key;
                 bool required = false;
                 for (uint32_t t = 0; t < MSK_NUM_TRIALS; ++t)
@@ -125,9 +123,9 @@ __global__ void __launch_bounds__(256) k_ms_wit_admit(MsApplyDev a, MsUpdateDev 
             }
             for (uint32_t t = 0; t < MSK_NUM_TRIALS; ++t) {
                 const uint64_t ci = (uint64_t)((mn + dist[t]) >> MSK_CHUNK_BITS);  // <= b1 + 255: exact
-                if (ci >= b0) continue;
+                if (ci >= s.b0) continue;
                 bool found = false;
-                for (uint64_t e = ebeg; e < eend; ++e) found |= u.chunk_index[e] == ci;
+                for (uint64_t e = ebeg; e < eend; ++e) found |= u.ch.chunk_index[e] == ci;
                 if (!found) absent = true;
             }
         }
@@ -155,7 +153,7 @@ __global__ void __launch_bounds__(256) k_ms_wit_paths(MsApplyDev a, MsUpdateDev 
         uint64_t T = 0;  // the job's touched chunks: groups [0, T), the same for every digest of a dictionary path
         if (accepted && !is_aocl) {
             const MsApplyJob& jb = a.jobs[u.wit_job[w]];
-            T = lb_group(a.aux + 2 * jb.grp_off, jb.n_grp, 0, sat_dec(jb.aocl_n) / MSK_BATCH_SIZE);
+            T = lb_group(a.aux + 2 * jb.grp_off, jb.n_grp, 0, MsJobScratch::batch_index(jb.aocl_n));
         }
         for (uint64_t tt = lane; tt < len; tt += LANES) {
             const uint32_t t = tt < 64 ? (uint32_t)tt : 64u;
@@ -164,18 +162,16 @@ __global__ void __launch_bounds__(256) k_ms_wit_paths(MsApplyDev a, MsUpdateDev 
             if (accepted) {
                 const uint32_t j = u.wit_job[w];
                 const MsApplyJob& jb = a.jobs[j];
-                const uint64_t n0 = jb.aocl_n, n1 = n0 + jb.k;
-                const uint64_t b0 = sat_dec(n0) / MSK_BATCH_SIZE, b1 = sat_dec(n1) / MSK_BATCH_SIZE;
-                const uint64_t slides = b1 - b0;
-                const uint64_t* d_aocl = a.dig + 5 * jb.dig_off;
-                const uint64_t* d_new = d_aocl + 5 * (jb.k + 1);
+                const MsJobScratch s(jb.aocl_n, jb.k);
+                const uint64_t n0 = s.n0, n1 = s.n1, b0 = s.b0, b1 = s.b1;
+                const uint64_t* dig = a.dig + 5 * jb.dig_off;  // the nodes k_ms_apply<true> kept, where s says
                 int r = NODE_MISSING;
                 if (t >= 63) {
                     // no path is that long: n1 < 2^64
                 } else if (is_aocl) {
                     const uint64_t l = u.aocl_leaf_index[w];
                     const uint64_t q = (l >> t) ^ 1ull;
-                    const AppendNodes m{n0, n1, a.additions + 5 * jb.add_off, d_aocl, a.carry + (size_t)j * 2 * 64 * 5,
+                    const AppendNodes m{n0, n1, a.additions + 5 * jb.add_off, dig + 5 * s.aocl(), a.carry + (size_t)j * 2 * 64 * 5,
                                         a.carry_mask[2 * (size_t)j]};
                     r = append_node(m, t, q, &src);
                     if (r == NODE_OLD) {
@@ -193,23 +189,22 @@ __global__ void __launch_bounds__(256) k_ms_wit_paths(MsApplyDev a, MsUpdateDev 
                 } else {
                     const uint64_t c = u.o_key[e];
                     const uint64_t q = (c >> t) ^ 1ull;
-                    const AppendNodes m{b0, b1, d_new, d_new + 5 * slides, a.carry + ((size_t)j * 2 + 1) * 64 * 5,
+                    const AppendNodes m{b0, b1, dig + 5 * s.fresh(), dig + 5 * s.fresh_levels(), a.carry + ((size_t)j * 2 + 1) * 64 * 5,
                                         a.carry_mask[2 * (size_t)j + 1]};
                     r = append_node(m, t, q, &src);
                     if (r == NODE_OLD) {
                         const uint64_t* aux = a.aux + 2 * jb.grp_off;
-                        const uint64_t* d_mut = d_new + 5 * (2 * slides + 1);
                         const uint64_t x = lb_group(aux, T, t, q);
                         const uint64_t se = u.o_ent_src[e];
                         if (x < T && (aux[2 * x + 1] >> t) == q) {  // a touched node
                             if (t <= ilog2_dev(aux[2 * x + 1] ^ b0)) {
-                                src = d_mut + 5 * ((uint64_t)t * jb.n_grp + x);
+                                src = dig + 5 * s.mut_node(jb.n_grp, t, x);
                                 r = NODE_HERE;
                             } else {
                                 r = NODE_MISSING;
                             }
-                        } else if (c < b0 && se != MSA_NONE && t < u.path_off[se + 1] - u.path_off[se]) {
-                            src = u.path + 5 * (u.path_off[se] + t);
+                        } else if (c < b0 && se != MSA_NONE && t < u.ch.path_off[se + 1] - u.ch.path_off[se]) {
+                            src = u.ch.path + 5 * (u.ch.path_off[se] + t);
                             r = NODE_HERE;
                         } else if (((b0 >> t) & 1) && q == (b0 >> t) - 1) {
                             src = a.peaks + 5 * (jb.swbf_peaks + peak_of_height(b0, t));
@@ -248,29 +243,28 @@ __global__ void __launch_bounds__(256) k_ms_wit_chunks(MsApplyDev a, MsUpdateDev
         if (ok) {
             const uint32_t j = u.wit_job[w];
             const MsApplyJob& jb = a.jobs[j];
-            const uint64_t n0 = jb.aocl_n, n1 = n0 + jb.k;
-            const uint64_t b0 = sat_dec(n0) / MSK_BATCH_SIZE, b1 = sat_dec(n1) / MSK_BATCH_SIZE;
+            const MsJobScratch s(jb.aocl_n, jb.k);
             ix = JobIndices{a.rec.minimum + 2 * jb.rec_off, a.rec.distances + MSK_NUM_TRIALS * jb.rec_off,
                             a.idx_perm + MSK_NUM_TRIALS * jb.rec_off};
             const uint64_t* aux = a.aux + 2 * jb.grp_off;
             const uint32_t* grp = a.grp + jb.grp_off + j;
-            const uint64_t T1 = lb_group(aux, jb.n_grp, 0, b1);
+            const uint64_t T1 = lb_group(aux, jb.n_grp, 0, s.b1);
             const uint64_t g = lb_group(aux, T1, 0, c);
             if (g < T1 && aux[2 * g + 1] == c) {
                 s0 = grp[g];
                 s1 = grp[g + 1];
             }
-            if (c < b0) {
+            if (c < s.b0) {
                 const uint64_t se = u.o_ent_src[e];
                 if (se == MSA_NONE) {
                     ok = false;  // not reached: the witness was admitted
                 } else {
-                    old = u.rel + u.rel_off[se];
-                    n_old = u.rel_off[se + 1] - u.rel_off[se];
+                    old = u.ch.rel + u.ch.rel_off[se];
+                    n_old = u.ch.rel_off[se + 1] - u.ch.rel_off[se];
                 }
-            } else if (c - b0 < MSK_WINDOW_CHUNKS) {
+            } else if (c - s.b0 < MSK_WINDOW_CHUNKS) {
                 const uint32_t* act = a.active + jb.act_off;
-                const uint64_t cc = c - b0;
+                const uint64_t cc = c - s.b0;
                 const uint64_t la = lb_u32(act, jb.n_active, cc << MSK_CHUNK_BITS);
                 old = act + la;
                 n_old = lb_u32(act, jb.n_active, (cc + 1) << MSK_CHUNK_BITS) - la;
@@ -317,34 +311,20 @@ __global__ void __launch_bounds__(256) k_ms_wit_seal(MsUpdateDev u, size_t witne
     }
 }
 
-static inline unsigned update_grid(size_t n) {
-    const size_t g = (n + 255) / 256;
-    return (unsigned)(g > 16384 ? 16384 : g);  // grid-stride beyond 16k workgroups
-}
-
 hipError_t launch_ms_wit_admit(const MsApplyDev& a, const MsUpdateDev& u, size_t witnesses, hipStream_t st) {
-    if (witnesses == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_wit_admit, dim3(update_grid(witnesses)), dim3(256), 0, st, a, u, witnesses);
-    return hipGetLastError();
+    return ms_launch(k_ms_wit_admit, witnesses, st, a, u, witnesses);
 }
 
 hipError_t launch_ms_wit_paths(const MsApplyDev& a, const MsUpdateDev& u, size_t witnesses, size_t entries, hipStream_t st) {
-    if (witnesses + entries == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_wit_paths, dim3(update_grid(8 * (witnesses + entries))), dim3(256), 0, st, a, u, witnesses,
-                       entries);  // 8 lanes per path
-    return hipGetLastError();
+    return ms_launch(k_ms_wit_paths, 8 * (witnesses + entries), st, a, u, witnesses, entries);  // 8 lanes per path
 }
 
 hipError_t launch_ms_wit_chunks(const MsApplyDev& a, const MsUpdateDev& u, size_t entries, hipStream_t st) {
-    if (entries == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_wit_chunks, dim3(update_grid(8 * entries)), dim3(256), 0, st, a, u, entries);  // 8 lanes per entry
-    return hipGetLastError();
+    return ms_launch(k_ms_wit_chunks, 8 * entries, st, a, u, entries);  // 8 lanes per entry
 }
 
 hipError_t launch_ms_wit_seal(const MsUpdateDev& u, size_t witnesses, hipStream_t st) {
-    if (witnesses == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ms_wit_seal, dim3(update_grid(witnesses)), dim3(256), 0, st, u, witnesses);
-    return hipGetLastError();
+    return ms_launch(k_ms_wit_seal, witnesses, st, u, witnesses);
 }
 
 }  // namespace nhip

@@ -136,9 +136,8 @@ class PackedChunks:
     rel: np.ndarray
 
     def _c(self):
-        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
-        return _lib.MsChunks(ptr(self.entry_off), ptr(self.chunk_index), ptr(self.path_off), ptr(self.path),
-                             ptr(self.rel_off), ptr(self.rel))
+        return _lib.MsChunks(_ptr(self.entry_off), _ptr(self.chunk_index), _ptr(self.path_off), _ptr(self.path),
+                             _ptr(self.rel_off), _ptr(self.rel))
 
 
 def pack_paths(paths: Sequence[Sequence[Sequence[int]]]) -> Tuple[np.ndarray, np.ndarray]:
@@ -204,12 +203,7 @@ def can_remove_batch(ctx, msa: MutatorSetAccumulator, records: Sequence[RemovalR
     if n == 0:
         return []
     cm, _keep = msa._c()
-    mn = np.zeros((n, 2), dtype=np.uint64)
-    dist = np.zeros((n, NUM_TRIALS), dtype=np.uint32)
-    for i, r in enumerate(records):
-        m = int(r.absolute_indices.minimum)
-        mn[i] = (m & (2 ** 64 - 1), m >> 64)
-        dist[i] = np.asarray(r.absolute_indices.distances, dtype=np.uint32)
+    mn, dist = _index_arrays(records)
     packed = pack_chunks(records)
     cc = packed._c()
     valid, can, status = (np.zeros(n, dtype=np.uint8) for _ in range(3))

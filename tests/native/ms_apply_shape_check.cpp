@@ -1,6 +1,7 @@
 // Host side of nhip_ms_apply_batch under ASan + UBSan (tests/test_ms_apply_ref.py): the shape validator
 // (csrc/ms_shape.cpp: ms_apply_ok) on good and malformed job batches, and the staged order (ms_apply_order
-// beside it) on the fixed batch and on seeded random ones against a naive recomputation.  Every array is
+// beside it) on the fixed batch and on seeded random ones against a naive recomputation, and the layout of a
+// job's digest scratch (MsJobScratch, ms_shape.hpp) against that order at chosen job sizes.  Every array is
 // an exactly sized heap block, so that a read past the declared shapes is a sanitizer report.  Host only:
 // links no HIP.
 #include <cstdio>
@@ -362,6 +363,80 @@ struct RandomBatch {
     }
 };
 
+// ---------------------------------------------------------------- the job's digest scratch (MsJobScratch)
+// One job per (aocl_n, k, n_grp) of the grid below and one whose aocl_n + k wraps: no record, one record inside
+// chunk 0, or one record with an index in each of 45 chunks.  MsJobScratch and ms_apply_order must agree on every
+// dig_off and on dig_total, with and without keep_nodes; the struct's bounds are compared with a recomputation
+// from the definitions, and its three regions must be disjoint and tile the total.
+void check_scratch() {
+    const uint64_t aocl_ns[] = {0, 1, 8, 9, (1ull << 13) + 1, 1ull << 63}, ks[] = {0, 1, 8, 64}, grps[] = {0, 1, 45};
+    struct Job {
+        uint64_t aocl_n, k, n_grp;
+    };
+    std::vector<Job> jobs;
+    for (uint64_t a : aocl_ns)
+        for (uint64_t k : ks)
+            for (uint64_t g : grps) jobs.push_back({a, k, g});
+    jobs.push_back({~0ull - 3, 8, 45});  // aocl_n + k wraps
+    const size_t n = jobs.size();
+    std::vector<nhip_msa> before(n);
+    std::vector<uint64_t> add_off = {0}, rec_off = {0}, minimum, entry_off = {0}, zero = {0};
+    std::vector<uint32_t> distances;
+    for (size_t j = 0; j < n; ++j) {
+        before[j] = nhip_msa{nhip_mmr{nullptr, 0, jobs[j].aocl_n}, nhip_mmr{nullptr, 0, 0}, nullptr, 0};
+        add_off.push_back(add_off.back() + jobs[j].k);
+        rec_off.push_back(rec_off.back() + (jobs[j].n_grp ? 1 : 0));
+        if (!jobs[j].n_grp) continue;
+        minimum.insert(minimum.end(), {0, 0});
+        for (uint32_t t = 0; t < 45; ++t) distances.push_back(jobs[j].n_grp == 1 ? t : 4096 * t);
+        entry_off.push_back(0);  // no dictionary entry
+    }
+    const std::vector<uint64_t> additions(5 * (size_t)add_off.back(), 1);
+    const nhip_ms_chunks chunks{ptr(entry_off), nullptr, ptr(zero), nullptr, ptr(zero), nullptr};
+    const nhip_ms_apply_in in{n, ptr(before), ptr(add_off), ptr(additions), ptr(rec_off), ptr(minimum), ptr(distances),
+                              &chunks, nullptr};
+    std::vector<uint8_t> verdict(n), status(n);
+    std::vector<uint64_t> bad_record(n);
+    nhip_ms_apply_out out{};
+    out.verdict = ptr(verdict);
+    out.status = ptr(status);
+    out.bad_record = ptr(bad_record);
+    const std::string what = "scratch";
+    size_t j = 0;
+    nhip::MsApplyCounts cnt;
+    CHECK(nhip::ms_apply_ok(&in, &out, &cnt) == NHIP_OK, "the batch is refused");
+    for (const bool keep : {false, true}) {
+        nhip::MsApplyOrder o;
+        nhip::ms_apply_order(&in, &out, cnt, &o, keep);
+        uint64_t dig = 0;
+        for (j = 0; j < n; ++j) {
+            const uint64_t n0 = jobs[j].aocl_n, k = jobs[j].k, g = jobs[j].n_grp, n1 = n0 + k;
+            const nhip::MsJobScratch s(n0, k);
+            CHECK(o.jobs[j].aocl_n == n0 && o.jobs[j].k == k && o.jobs[j].n_grp == g, "the job is not the case");
+            CHECK(o.jobs[j].dig_off == dig, "dig_off");
+            // the bounds, from get_batch_index = (num_leafs - 1) / BATCH_SIZE, saturating at 0
+            const uint64_t b0 = n0 ? (n0 - 1) / 8 : 0, b1 = n1 ? (n1 - 1) / 8 : 0;
+            CHECK(s.n0 == n0 && s.n1 == n1 && s.b0 == b0 && s.b1 == b1, "n0 / n1 / b0 / b1");
+            CHECK(s.wrapped() == (j == n - 1) && s.slides == (s.wrapped() ? 0 : b1 - b0), "wrapped / slides");
+            // aocl | fresh | mut: each begins where the one before ends, none is empty but mut, the last ends at total
+            uint64_t levels = 2;
+            if (keep)
+                for (levels = 1; (b0 >> (levels - 1)) != 0; ++levels) {
+                }
+            CHECK(s.aocl() == 0 && s.fresh() == s.aocl() + k + 1 && s.mut() == s.fresh() + 2 * s.slides + 1 &&
+                      s.total(g, keep) == s.mut() + levels * g,
+                  "the regions do not tile the total");
+            CHECK(s.fresh() <= s.fresh_levels() && s.fresh_levels() + s.slides + 1 == s.mut(), "fresh_levels");
+            CHECK(s.mut_stride(g) == g && s.mut_node(g, 0, 0) == s.mut(), "the first mutation node");
+            if (g) CHECK(s.mut_node(g, levels - 1, g - 1) + 1 == s.total(g, keep), "the last mutation node");
+            dig += s.total(g, keep);
+        }
+        j = n;
+        CHECK(o.dig_total == dig, "dig_total");
+        ++good;
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -463,6 +538,7 @@ int main() {
         RandomBatch b(seed, seed == 7 ? HIGH_WORD : seed == 11 ? CROSS_2_64 : PLAIN);
         check_order(b.in(), b.out(), "random batch " + std::to_string(seed));
     }
+    check_scratch();
     std::printf("good %d bad %d\n", good, bad);
     return failures ? 1 : 0;
 }
