@@ -907,6 +907,106 @@ int nhip_ms_update_plan(const nhip_ms_apply_in *block, const nhip_ms_update_in *
 int nhip_ms_update_batch(nhip_ctx *ctx, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out,
                          const nhip_ms_update_in *wit, nhip_ms_updated *out);
 
+/* ---- a block file's mutator-set and transaction rules ---------------------------
+ * Block::validate rules 2.a-2.l (protocol/consensus/block/mod.rs:811-891) for every (parent, child) pair of
+ * scanned blocks, from the file's bytes: msa_before is the parent's Block::mutator_set_accumulator_after
+ * (mod.rs:369-378,816), i.e. the parent body's accumulator plus the parent's two guesser-fee addition records
+ * (block_kernel.rs:47-93).  Every digest is computed on the device and every status is the device's.
+ *
+ * nhip_blk_ms_params: NativeCurrency.hash() and TimeLock.hash() (type_scripts/native_currency.rs,
+ * time_lock.rs) come from tasm-lib code generation, so they are parameters, canonical digests; the limit of
+ * rules 2.j-2.l is MAX_NUM_INPUTS_OUTPUTS_ANNOUNCEMENTS = 1 << 14 (consensus_rule_set.rs:71-91). */
+typedef struct {
+    uint64_t native_currency_hash[5], time_lock_hash[5];
+    uint32_t pow_tree_height;
+    uint32_t max_num_inputs, max_num_outputs, max_num_announcements;
+} nhip_blk_ms_params;
+/* both digests zero (the caller fills them in), pow_tree_height 29, the three limits 1 << 14 */
+void nhip_blk_ms_params_default(nhip_blk_ms_params *out);
+/* nhip_blk_ms_walk (host only, hashes nothing): what rules 2.a-2.l and the guesser-fee records read of n scanned
+ * blocks (blocks[i] from nhip_blk_scan of the same bytes with the same pow_tree_height <= 64; each is parsed
+ * again from its offset, a malformed one is NHIP_ERR_DECODE), as integers and byte copies only.  Per block: the
+ * header's height, timestamp and guesser_receiver_data; the kernel's fee and coinbase (i128 as two u64, low
+ * first; coinbase_tag is the Option tag), timestamp and announcement count; the body's
+ * mutator_set_accumulator (peak counts as serialized, saturated at 65; at most 64 peaks are stored, in 64
+ * slots per block); the kernel's outputs (canonical commitments) and its inputs as they lie in the file, i.e.
+ * in the packed reading of DESIGN.md §6f: rec_off / minimum / distances and the dictionaries with an entry's
+ * key in chunk_index.  Two-call sizing, as nhip_ms_unpack_plan: with every array pointer NULL only the totals
+ * are written; otherwise every array is present with its capacity, and NHIP_ERR_ARG if one is too small. */
+typedef struct {
+    uint64_t *height, *timestamp;                  /* n each */
+    uint64_t *receiver_digest, *lock_script_hash;  /* n x 5 */
+    uint64_t *fee, *coinbase;                      /* n x 2 */
+    uint8_t *coinbase_tag;                         /* n */
+    uint64_t *kernel_timestamp, *n_announcements;  /* n */
+    uint64_t *aocl_num_leafs, *swbf_num_leafs;     /* n */
+    uint32_t *aocl_n_peaks, *swbf_n_peaks;         /* n */
+    uint64_t *aocl_peaks, *swbf_peaks;             /* n x 64 digests */
+    uint64_t *active_off;                          /* n + 1, in u32 */
+    uint32_t *active;                              /* active_cap: ActiveWindow::sbf */
+    uint64_t *out_off;                             /* n + 1, in addition records */
+    uint64_t *outputs;                             /* outputs_cap digests */
+    uint64_t *rec_off;                             /* n + 1, in removal records */
+    uint64_t *minimum;                             /* records_cap x 2 */
+    uint32_t *distances;                           /* records_cap x 45 */
+    uint64_t *entry_off;                           /* records_cap + 1 */
+    uint64_t *chunk_index;                         /* entries_cap */
+    uint64_t *path_off;                            /* entries_cap + 1, in digests */
+    uint64_t *path;                                /* path_cap digests */
+    uint64_t *rel_off;                             /* entries_cap + 1, in u32 */
+    uint32_t *rel;                                 /* rel_cap */
+    size_t active_cap, outputs_cap, records_cap, entries_cap, path_cap, rel_cap;
+    size_t active_words, n_outputs, records, entries, path_digests, rel_words; /* out: the totals */
+} nhip_blk_ms_parts;
+int nhip_blk_ms_walk(const uint8_t *bytes, size_t n_bytes, uint32_t pow_tree_height, const nhip_blk_block *blocks,
+                     size_t n, nhip_blk_ms_parts *out);
+/* status of a block's guesser-fee records */
+enum {
+    NHIP_GUESSER_OK = 0,
+    NHIP_GUESSER_NEGATIVE_FEE = 1 /* BlockBody::total_guesser_reward (block_body.rs:160-169): no records */
+};
+/* BlockKernel::guesser_fee_addition_records (block_kernel.rs:47-93) of n scanned blocks, one lane per (block,
+ * UTXO): records[i] = [locked, unlocked], each commit(Tip5::hash(utxo), Block::hash, receiver_digest)
+ * (util_types/mutator_set.rs:49-54), with timelocked = fee / 2, unlocked = fee - timelocked and the time lock
+ * until header.timestamp + Timestamp::years(3) (a Goldilocks sum).  n_records[i] is 2, or 0 for a block at
+ * height 0 or with a negative fee (its records are then zero); status[i] is NHIP_GUESSER_*.  digests: n x 5 as
+ * nhip_blk_digests or nhip_blk_chain_check wrote them, or NULL to compute them here through nhip_blk_digests'
+ * code (pow_tree_height <= 32).  The Utxo / Coin encodings are unpinned. */
+int nhip_blk_guesser_fee_records(nhip_ctx *ctx, const uint8_t *bytes, size_t n_bytes, const nhip_blk_ms_params *params,
+                                 const nhip_blk_block *blocks, size_t n, const uint64_t *digests, uint64_t *records,
+                                 uint8_t *n_records, uint8_t *status);
+/* block_validation_error.rs, in rule order; the first rule that fails is the status */
+enum {
+    NHIP_BLKMS_OK = 0,
+    NHIP_BLKMS_SKIPPED = 1,                  /* parent_of[i] == -1: nothing checked */
+    NHIP_BLKMS_UNPACK = 2,                   /* 2.a; ms_status = NHIP_MS_UNPACK_* */
+    NHIP_BLKMS_PARENT_NEGATIVE_FEE = 3,      /* the `?` of mod.rs:816 */
+    NHIP_BLKMS_PARENT_MSA_INCONSISTENT = 4,  /* divergence, failing closed (NHIP_MS_INCONSISTENT): also a parent
+                                                accumulator with more than 64 peaks */
+    NHIP_BLKMS_REMOVAL_RECORDS_VALIDITY = 5,   /* 2.b; ms_status = the first failing record's, bad_record = it */
+    NHIP_BLKMS_REMOVAL_RECORDS_UNIQUENESS = 6, /* 2.c */
+    NHIP_BLKMS_UPDATE_IMPOSSIBLE = 7,          /* 2.d */
+    NHIP_BLKMS_UPDATE_INTEGRITY = 8,           /* 2.e; also a claimed accumulator with more than 64 peaks */
+    NHIP_BLKMS_TRANSACTION_TIMESTAMP = 9,      /* 2.f */
+    NHIP_BLKMS_COINBASE_TOO_BIG = 10,          /* 2.g */
+    NHIP_BLKMS_NEGATIVE_COINBASE = 11,         /* 2.h */
+    NHIP_BLKMS_NEGATIVE_FEE = 12,              /* 2.i */
+    NHIP_BLKMS_TOO_MANY_INPUTS = 13,           /* 2.j: the unpacked inputs */
+    NHIP_BLKMS_TOO_MANY_OUTPUTS = 14,          /* 2.k */
+    NHIP_BLKMS_TOO_MANY_ANNOUNCEMENTS = 15     /* 2.l */
+};
+/* Rules 2.a-2.l for every (blocks[parent_of[i]], blocks[i]) pair: status[i] is NHIP_BLKMS_*, ms_status[i] the
+ * NHIP_MS_* detail of rules 2.a-2.e (NHIP_MS_OK otherwise) and bad_record[i] the record nhip_ms_apply_batch_packed
+ * blames (UINT64_MAX: none).  k_guesser_fee_records makes every block's records; pass A is nhip_ms_apply_batch over
+ * (the parent body's accumulator, its records, no removals); pass B is nhip_ms_apply_batch_packed over (pass A's
+ * accumulator, the child's packed inputs, its outputs, its body's accumulator as the expected one);
+ * k_blk_ms_rules evaluates 2.f-2.l and combines the statuses.  Pass A's accumulators cross to the host between the
+ * passes; the records' paths and chunks never do.  digests as above.  A parent index outside -1..n-1 or a null
+ * pointer with a non-zero count is NHIP_ERR_ARG and a malformed block NHIP_ERR_DECODE, the outputs untouched. */
+int nhip_blk_ms_check(nhip_ctx *ctx, const uint8_t *bytes, size_t n_bytes, const nhip_blk_ms_params *params,
+                      const nhip_blk_block *blocks, size_t n, const int64_t *parent_of, const uint64_t *digests,
+                      uint8_t *status, uint8_t *ms_status, uint64_t *bad_record);
+
 /* ---- kernel timing (HIP events on the ctx stream around every kernel launch) ------------ */
 int nhip_timing_enable(nhip_ctx *ctx, int on);
 /* Total device time of the kernels launched since the last reset, and their count. */

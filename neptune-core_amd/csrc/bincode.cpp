@@ -51,6 +51,7 @@
 #include <vector>
 
 #include "../../include/neptune_hip.h"
+#include "blk_ms_parts.hpp"
 #include "chain_rules.hpp"
 
 namespace {
@@ -675,6 +676,139 @@ int blk_sequences_into(const uint8_t* bytes, size_t n_bytes, uint32_t pow_tree_h
     if (!ok) return NHIP_ERR_DECODE;
     offsets[0] = 0;
     for (int i = 0; i < 11; ++i) offsets[i + 1] = ends[i];
+    return NHIP_OK;
+}
+}  // namespace nhip
+
+// ---- the mutator-set and transaction parts of a block: integers and byte copies only
+namespace {
+// MmrAccumulator into 64 peak slots; the count as serialized, saturated at 65 (as nhip_blk_header's mmr_n_peaks)
+void mmr_parts(Rd& r, uint64_t& num_leafs, uint32_t& n_peaks, std::vector<uint64_t>& slots) {
+    num_leafs = r.u64();
+    const uint64_t np = r.len(40);
+    n_peaks = (uint32_t)std::min<uint64_t>(np, 65);
+    const size_t at = slots.size();
+    slots.resize(at + 64 * 5, 0);
+    for (uint64_t i = 0; i < np && r.ok; ++i) {
+        uint64_t d[5];
+        r.digest(d);
+        if (i < 64) std::memcpy(slots.data() + at + 5 * i, d, 40);
+    }
+}
+}  // namespace
+
+namespace nhip {
+int blk_ms_walk_block(const uint8_t* bytes, size_t n_bytes, uint32_t pow_tree_height, uint64_t offset, BlkMsParts& p) {
+    Rd r{bytes, n_bytes, (size_t)offset};
+    BlkMsParts b;  // this block alone: p is touched only once it has parsed
+    r.bfe();       // version
+    b.height.push_back(r.bfe());
+    r.skip(40);  // prev_block_digest
+    b.timestamp.push_back(r.bfe());
+    // pow: root, path_a, path_b, nonce; cumulative_proof_of_work [u32; 6]; difficulty [u32; 5]
+    r.skip(40ull * (2ull * pow_tree_height + 2) + 4 * 6 + 4 * 5);
+    uint64_t d[5];
+    r.digest(d);
+    b.receiver_digest.assign(d, d + 5);
+    r.digest(d);
+    b.lock_script_hash.assign(d, d + 5);
+    // transaction kernel: inputs as they lie (the packed reading of §6f), outputs, announcements, fee, coinbase, timestamp
+    const uint64_t n_in = r.len(16 + 4 * NUM_TRIALS + 8);
+    for (uint64_t i = 0; i < n_in && r.ok; ++i) {
+        uint64_t lo, hi;
+        r.u128(lo, hi);
+        b.minimum.push_back(lo);
+        b.minimum.push_back(hi);
+        for (uint32_t k = 0; k < NUM_TRIALS; ++k) b.distances.push_back(r.u32());
+        const uint64_t n_ent = r.len(8 + 8 + 8);
+        for (uint64_t e = 0; e < n_ent && r.ok; ++e) {
+            b.chunk_index.push_back(r.u64());
+            const uint64_t np = r.len(40);
+            for (uint64_t k = 0; k < np && r.ok; ++k) {
+                r.digest(d);
+                b.path.insert(b.path.end(), d, d + 5);
+            }
+            b.path_off.push_back(b.path.size() / 5);
+            const uint64_t nr = r.len(4);
+            for (uint64_t k = 0; k < nr && r.ok; ++k) b.rel.push_back(r.u32());
+            b.rel_off.push_back(b.rel.size());
+        }
+        b.entry_off.push_back(b.chunk_index.size());
+    }
+    const uint64_t n_out = r.len(40);
+    for (uint64_t i = 0; i < n_out && r.ok; ++i) {
+        r.digest(d);
+        b.outputs.insert(b.outputs.end(), d, d + 5);
+    }
+    const uint64_t n_ann = r.len(8);
+    for (uint64_t i = 0; i < n_ann && r.ok; ++i) r.skip(8 * r.len(8));
+    b.n_announcements.push_back(n_ann);
+    uint64_t lo, hi;
+    r.u128(lo, hi);
+    b.fee = {lo, hi};
+    const uint8_t tag = r.u8();
+    if (tag > 1) r.ok = false;
+    lo = hi = 0;
+    if (tag == 1) r.u128(lo, hi);
+    b.coinbase_tag.push_back(tag);
+    b.coinbase = {lo, hi};
+    b.kernel_timestamp.push_back(r.bfe());
+    r.skip(40);    // mutator_set_hash
+    r.boolean();   // merge_bit
+    // body: mutator_set_accumulator {aocl, swbf_inactive, swbf_active {sbf}}
+    uint64_t nl;
+    uint32_t np;
+    mmr_parts(r, nl, np, b.aocl_peaks);
+    b.aocl_num_leafs.push_back(nl);
+    b.aocl_n_peaks.push_back(np);
+    mmr_parts(r, nl, np, b.swbf_peaks);
+    b.swbf_num_leafs.push_back(nl);
+    b.swbf_n_peaks.push_back(np);
+    const uint64_t na = r.len(4);
+    for (uint64_t i = 0; i < na && r.ok; ++i) b.active.push_back(r.u32());
+    // the rest of the block must parse too: a block that nhip_blk_scan refuses is refused here
+    mmr_accumulator(r, nullptr);  // lock_free_mmr_accumulator
+    mmr_accumulator(r, nullptr);  // block_mmr_accumulator
+    const uint64_t nc = r.len(40 + 4 + 16);
+    for (uint64_t i = 0; i < nc && r.ok; ++i) claim_skip(r);
+    const uint32_t kind = r.variant(3);
+    if (r.ok && kind == NHIP_BLOCK_PROOF_SINGLE) r.skip(8 * r.len(8));
+    if (!r.ok) return NHIP_ERR_DECODE;
+
+    auto cat = [](auto& dst, const auto& src) { dst.insert(dst.end(), src.begin(), src.end()); };
+    auto cat_off = [](std::vector<uint64_t>& dst, const std::vector<uint64_t>& src) {  // src[0] == 0 is dst's last
+        const uint64_t base = dst.back();
+        for (size_t k = 1; k < src.size(); ++k) dst.push_back(base + src[k]);
+    };
+    cat(p.height, b.height);
+    cat(p.timestamp, b.timestamp);
+    cat(p.receiver_digest, b.receiver_digest);
+    cat(p.lock_script_hash, b.lock_script_hash);
+    cat(p.fee, b.fee);
+    cat(p.coinbase, b.coinbase);
+    cat(p.coinbase_tag, b.coinbase_tag);
+    cat(p.kernel_timestamp, b.kernel_timestamp);
+    cat(p.n_announcements, b.n_announcements);
+    cat(p.aocl_num_leafs, b.aocl_num_leafs);
+    cat(p.swbf_num_leafs, b.swbf_num_leafs);
+    cat(p.aocl_n_peaks, b.aocl_n_peaks);
+    cat(p.swbf_n_peaks, b.swbf_n_peaks);
+    cat(p.aocl_peaks, b.aocl_peaks);
+    cat(p.swbf_peaks, b.swbf_peaks);
+    cat(p.active, b.active);
+    p.active_off.push_back(p.active.size());
+    cat(p.outputs, b.outputs);
+    p.out_off.push_back(p.outputs.size() / 5);
+    cat(p.minimum, b.minimum);
+    cat(p.distances, b.distances);
+    p.rec_off.push_back(p.minimum.size() / 2);
+    cat_off(p.entry_off, b.entry_off);
+    cat_off(p.path_off, b.path_off);
+    cat_off(p.rel_off, b.rel_off);
+    cat(p.chunk_index, b.chunk_index);
+    cat(p.path, b.path);
+    cat(p.rel, b.rel);
+    ++p.n;
     return NHIP_OK;
 }
 }  // namespace nhip

@@ -184,6 +184,32 @@ class MsUpdated(ctypes.Structure):
                 ("path_digests", ctypes.c_size_t), ("rel_words", ctypes.c_size_t)]
 
 
+class BlkMsParams(ctypes.Structure):
+    """nhip_blk_ms_params: the type-script digests, the pow tree height and the limits of rules 2.j-2.l."""
+    _fields_ = [("native_currency_hash", ctypes.c_uint64 * 5), ("time_lock_hash", ctypes.c_uint64 * 5),
+                ("pow_tree_height", ctypes.c_uint32), ("max_num_inputs", ctypes.c_uint32),
+                ("max_num_outputs", ctypes.c_uint32), ("max_num_announcements", ctypes.c_uint32)]
+
+
+class BlkMsParts(ctypes.Structure):
+    """nhip_blk_ms_parts: what nhip_blk_ms_walk extracts of n scanned blocks (28 arrays, 6 capacities, 6 totals)."""
+    ARRAYS = ("height", "timestamp", "receiver_digest", "lock_script_hash", "fee", "coinbase", "coinbase_tag",
+              "kernel_timestamp", "n_announcements", "aocl_num_leafs", "swbf_num_leafs", "aocl_n_peaks", "swbf_n_peaks",
+              "aocl_peaks", "swbf_peaks", "active_off", "active", "out_off", "outputs", "rec_off", "minimum", "distances",
+              "entry_off", "chunk_index", "path_off", "path", "rel_off", "rel")
+    CAPS = ("active_cap", "outputs_cap", "records_cap", "entries_cap", "path_cap", "rel_cap")
+    TOTALS = ("active_words", "n_outputs", "records", "entries", "path_digests", "rel_words")
+    _fields_ = [(f, ctypes.c_void_p) for f in ARRAYS] + [(f, ctypes.c_size_t) for f in CAPS + TOTALS]
+
+
+NHIP_GUESSER_OK, NHIP_GUESSER_NEGATIVE_FEE = 0, 1
+NHIP_BLKMS_OK, NHIP_BLKMS_SKIPPED, NHIP_BLKMS_UNPACK, NHIP_BLKMS_PARENT_NEGATIVE_FEE, NHIP_BLKMS_PARENT_MSA_INCONSISTENT, \
+    NHIP_BLKMS_REMOVAL_RECORDS_VALIDITY, NHIP_BLKMS_REMOVAL_RECORDS_UNIQUENESS, NHIP_BLKMS_UPDATE_IMPOSSIBLE, \
+    NHIP_BLKMS_UPDATE_INTEGRITY, NHIP_BLKMS_TRANSACTION_TIMESTAMP, NHIP_BLKMS_COINBASE_TOO_BIG, \
+    NHIP_BLKMS_NEGATIVE_COINBASE, NHIP_BLKMS_NEGATIVE_FEE, NHIP_BLKMS_TOO_MANY_INPUTS, NHIP_BLKMS_TOO_MANY_OUTPUTS, \
+    NHIP_BLKMS_TOO_MANY_ANNOUNCEMENTS = range(16)
+
+
 _pp = ctypes.POINTER(ctypes.c_void_p)
 
 # (name, argtypes) for every symbol of include/neptune_hip.h
@@ -328,6 +354,11 @@ SIGNATURES = {
                                 ctypes.c_int),
     "nhip_blk_digests": ([_vp, _vp, _sz, ctypes.c_uint32, _vp, _sz, _vp, _vp], ctypes.c_int),
     "nhip_blk_chain_check": ([_vp, _vp, _sz, ctypes.POINTER(ChainParams), _vp, _sz, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "nhip_blk_ms_params_default": ([ctypes.POINTER(BlkMsParams)], None),
+    "nhip_blk_ms_walk": ([_vp, _sz, ctypes.c_uint32, _vp, _sz, ctypes.POINTER(BlkMsParts)], ctypes.c_int),
+    "nhip_blk_guesser_fee_records": ([_vp, _vp, _sz, ctypes.POINTER(BlkMsParams), _vp, _sz, _vp, _vp, _vp, _vp],
+                                     ctypes.c_int),
+    "nhip_blk_ms_check": ([_vp, _vp, _sz, ctypes.POINTER(BlkMsParams), _vp, _sz, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "nhip_le_words": ([_vp, _sz, ctypes.c_uint64, _sz, _vp], ctypes.c_int),
     "nhip_le_words_gpu": ([_vp, _vp, _sz, ctypes.POINTER(Span), _sz, _vp], ctypes.c_int),
     "nhip_wire_scan_txs": ([_vp, _sz, _sz, ctypes.POINTER(Span), _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz),

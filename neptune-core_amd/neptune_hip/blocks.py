@@ -14,6 +14,9 @@ natively (csrc/bincode.cpp) straight into the verifier's inputs.
   `verifier.transactions_are_valid`.
 * `block_digests` / `chain_links` / `chain_params` — `Block::hash`, and `Block::validate` rules 0.a-0.g with
   `Block::has_proof_of_work` for every (parent, child) pair of a file, each one call (DESIGN.md §6e).
+* `guesser_fee_addition_records` / `mutator_set_links` / `validate_chain_file` — the parent's guesser-fee addition
+  records, and `Block::validate` rules 2.a-2.l for every (parent, child) pair of a file, each one call over the
+  file's bytes; `mutator_set_parts` is the host walk behind them.
 Proof words are copied once, reduced mod p, from the file bytes into numpy buffers that the
 verifier stages without further conversion, or, given an `arena` (`stark.Arena`, round 6), straight
 into pinned memory on a GPU's NUMA node (nhip_arena_ingest_blocks / _spans), from where the
@@ -271,6 +274,144 @@ def accumulator_after(ctx, msa, guesser_fee_addition_records):
     if not verdict:
         raise ValueError(f"mutator set accumulator rejected: status {status}")
     return after
+
+
+# ---------------------------------------------------------------- mutator-set and transaction rules
+BLKMS_OK, BLKMS_SKIPPED, BLKMS_UNPACK, BLKMS_PARENT_NEGATIVE_FEE, BLKMS_PARENT_MSA_INCONSISTENT, \
+    BLKMS_REMOVAL_RECORDS_VALIDITY, BLKMS_REMOVAL_RECORDS_UNIQUENESS, BLKMS_UPDATE_IMPOSSIBLE, BLKMS_UPDATE_INTEGRITY, \
+    BLKMS_TRANSACTION_TIMESTAMP, BLKMS_COINBASE_TOO_BIG, BLKMS_NEGATIVE_COINBASE, BLKMS_NEGATIVE_FEE, \
+    BLKMS_TOO_MANY_INPUTS, BLKMS_TOO_MANY_OUTPUTS, BLKMS_TOO_MANY_ANNOUNCEMENTS = range(16)
+# the rule each status stands for, as `validate_chain_file` names it
+BLKMS_RULES = (None, None, "2.a", "2.b parent fee", "2.b parent accumulator", "2.b", "2.c", "2.d", "2.e", "2.f", "2.g",
+               "2.h", "2.i", "2.j", "2.k", "2.l")
+LINK_RULES = (None, None, "0.a", "0.b", "0.c", "0.d", "0.e", "0.f", "0.g")
+GUESSER_OK, GUESSER_NEGATIVE_FEE = 0, 1
+
+
+def ms_params(type_scripts, pow_tree_height: int = POW_TREE_HEIGHT, max_num: Optional[int] = None) -> "_lib.BlkMsParams":
+    """`nhip_blk_ms_params`.  `type_scripts`: `(NativeCurrency.hash(), TimeLock.hash())`, two digests that come from
+    tasm-lib code generation (as `verifier.ConsensusPrograms`), or a ready `BlkMsParams`, returned as it is.
+    `max_num`: one value for the three limits of rules 2.j-2.l instead of 1 << 14."""
+    if isinstance(type_scripts, _lib.BlkMsParams):
+        return type_scripts
+    native_currency, time_lock = type_scripts
+    p = _lib.BlkMsParams()
+    _lib.load().nhip_blk_ms_params_default(ctypes.byref(p))
+    for q in range(5):
+        p.native_currency_hash[q], p.time_lock_hash[q] = int(native_currency[q]), int(time_lock[q])
+    p.pow_tree_height = pow_tree_height
+    if max_num is not None:
+        p.max_num_inputs = p.max_num_outputs = p.max_num_announcements = int(max_num)
+    return p
+
+
+_PARTS_DTYPES = dict(coinbase_tag=np.uint8, aocl_n_peaks=np.uint32, swbf_n_peaks=np.uint32, active=np.uint32,
+                     distances=np.uint32, rel=np.uint32)
+
+
+def mutator_set_parts(data, records: Sequence[BlockRecord], pow_tree_height: int = POW_TREE_HEIGHT) -> dict:
+    """The host walk `nhip_blk_ms_walk` (no GPU, hashes nothing): what rules 2.a-2.l and the guesser-fee records read
+    of every record of `data`, as numpy arrays named and shaped as `nhip_blk_ms_parts` says.  The inputs are the
+    packed list as it lies in the file (an entry's key in `chunk_index`)."""
+    lib = _lib.load()
+    a, n = _buf(data)
+    m = len(records)
+    blocks = ctypes.cast(_scanned(records), ctypes.c_void_p)
+    out = _lib.BlkMsParts()
+    rc = lib.nhip_blk_ms_walk(a.ctypes.data, n, pow_tree_height, blocks, m, ctypes.byref(out))
+    if rc == NHIP_ERR_DECODE:
+        raise BlockFileError("malformed block", 0)
+    check(rc, "nhip_blk_ms_walk")
+    A, O, R, E, PD, W = (int(getattr(out, f)) for f in _lib.BlkMsParts.TOTALS)
+    shapes = dict(height=(m,), timestamp=(m,), receiver_digest=(m, 5), lock_script_hash=(m, 5), fee=(m, 2),
+                  coinbase=(m, 2), coinbase_tag=(m,), kernel_timestamp=(m,), n_announcements=(m,), aocl_num_leafs=(m,),
+                  swbf_num_leafs=(m,), aocl_n_peaks=(m,), swbf_n_peaks=(m,), aocl_peaks=(m, 64, 5), swbf_peaks=(m, 64, 5),
+                  active_off=(m + 1,), active=(A,), out_off=(m + 1,), outputs=(O, 5), rec_off=(m + 1,), minimum=(R, 2),
+                  distances=(R, 45), entry_off=(R + 1,), chunk_index=(E,), path_off=(E + 1,), path=(PD, 5),
+                  rel_off=(E + 1,), rel=(W,))
+    arrays = {f: np.zeros(shapes[f], dtype=_PARTS_DTYPES.get(f, np.uint64)) for f in _lib.BlkMsParts.ARRAYS}
+    # a zero-size array still gets an address: only the count pass has null array pointers
+    pad = {f: (v if v.size else np.zeros(1, dtype=v.dtype)) for f, v in arrays.items()}
+    out = _lib.BlkMsParts(*(pad[f].ctypes.data for f in _lib.BlkMsParts.ARRAYS), A, O, R, E, PD, W)
+    check(lib.nhip_blk_ms_walk(a.ctypes.data, n, pow_tree_height, blocks, m, ctypes.byref(out)), "nhip_blk_ms_walk")
+    return arrays
+
+
+def _digest_arg(digests, m):
+    if digests is None:
+        return None, None
+    d = np.ascontiguousarray(np.asarray(digests, dtype=np.uint64)).reshape(-1, 5)
+    if d.shape[0] != m:
+        raise ValueError("digests needs one digest per record")
+    return d, (d.ctypes.data if m else None)
+
+
+def guesser_fee_addition_records(ctx, data, records: Sequence[BlockRecord], type_scripts, digests=None,
+                                 pow_tree_height: int = POW_TREE_HEIGHT):
+    """`BlockKernel::guesser_fee_addition_records` (block_kernel.rs:47-93) of every record of `data` in one call
+    (`nhip_blk_guesser_fee_records`): per block `(status, [locked, unlocked])` with `status` one of `GUESSER_*` and the
+    list empty for a block at height 0 or with a negative fee.  `digests`: the blocks' `Block::hash` as
+    `block_digests` or `nhip_blk_chain_check` gave them; by default they are computed here."""
+    a, n = _buf(data)
+    m = len(records)
+    p = ms_params(type_scripts, pow_tree_height)
+    _keep, dptr = _digest_arg(digests, m)
+    rec = np.zeros((max(m, 1), 2, 5), dtype=np.uint64)
+    nrec, status = np.zeros(max(m, 1), dtype=np.uint8), np.zeros(max(m, 1), dtype=np.uint8)
+    check(ctx.lib.nhip_blk_guesser_fee_records(ctx.handle, a.ctypes.data, n, ctypes.byref(p),
+                                               ctypes.cast(_scanned(records), ctypes.c_void_p), m, dptr, rec.ctypes.data,
+                                               nrec.ctypes.data, status.ctypes.data), "nhip_blk_guesser_fee_records")
+    return [(int(status[i]), [tuple(int(x) for x in rec[i, k]) for k in range(int(nrec[i]))]) for i in range(m)]
+
+
+def mutator_set_links(ctx, data, records: Sequence[BlockRecord], type_scripts, parent_of=None, digests=None,
+                      pow_tree_height: int = POW_TREE_HEIGHT) -> List[Tuple[int, int, Optional[int]]]:
+    """`Block::validate` rules 2.a-2.l (block/mod.rs:811-891) for every (parent, child) pair of `records` in one call
+    (`nhip_blk_ms_check`): `[(status, ms_status, bad_record)]` with `status` one of `BLKMS_*`, `ms_status` the
+    `neptune_hip.mutator_set` status behind rules 2.a-2.e and `bad_record` the input it blames (None: none).
+    `parent_of` and `digests` as in `chain_links` and `guesser_fee_addition_records`."""
+    a, n = _buf(data)
+    m = len(records)
+    par = np.arange(-1, m - 1, dtype=np.int64) if parent_of is None else np.asarray(parent_of, dtype=np.int64)
+    if par.shape != (m,):
+        raise ValueError("parent_of needs one entry per record")
+    par = np.ascontiguousarray(par) if m else np.zeros(1, dtype=np.int64)
+    p = ms_params(type_scripts, pow_tree_height)
+    _keep, dptr = _digest_arg(digests, m)
+    status, ms_status = np.zeros(max(m, 1), dtype=np.uint8), np.zeros(max(m, 1), dtype=np.uint8)
+    bad = np.zeros(max(m, 1), dtype=np.uint64)
+    check(ctx.lib.nhip_blk_ms_check(ctx.handle, a.ctypes.data, n, ctypes.byref(p),
+                                    ctypes.cast(_scanned(records), ctypes.c_void_p), m, par.ctypes.data, dptr,
+                                    status.ctypes.data, ms_status.ctypes.data, bad.ctypes.data), "nhip_blk_ms_check")
+    return [(int(status[i]), int(ms_status[i]), None if int(bad[i]) == 2 ** 64 - 1 else int(bad[i])) for i in range(m)]
+
+
+def validate_chain_file(ctx, path: str, verifier, programs, type_scripts, now: int, network=None,
+                        pow_tree_height: int = POW_TREE_HEIGHT) -> List[Optional[str]]:
+    """`Block::validate` over one blk file, every block against the block before it (the first block's pair is
+    skipped: only its rules 1.a-1.d are checked): `chain_links`, `validate_block_proofs` and `mutator_set_links`, each
+    one pass over the file.  Per block the first failing rule in the reference's order (0.x, the proof of work, 1.x,
+    2.x), as a string, or None.  Rule 1.e (the block's size) is not covered."""
+    from .verifier import Network, validate_block_proofs
+    network = network if network is not None else Network.MAIN
+    if os.path.getsize(path) == 0:
+        return []
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as m:
+        recs = blocks_from_bytes(m, pow_tree_height)
+        links = chain_links(ctx, m, recs, network, now, pow_tree_height=pow_tree_height)
+        proofs = validate_block_proofs(ctx, blocks_to_validate(ctx, recs), verifier, programs, network)
+        ms = mutator_set_links(ctx, m, recs, type_scripts, pow_tree_height=pow_tree_height)
+    out: List[Optional[str]] = []
+    for (link, pow_ok), proof, (st, _, _) in zip(links, proofs, ms):
+        if LINK_RULES[link] is not None:
+            out.append(LINK_RULES[link])
+        elif link != LINK_SKIPPED and not pow_ok:
+            out.append("proof of work")
+        elif proof is not None:
+            out.append(proof)
+        else:
+            out.append(BLKMS_RULES[st])
+    return out
 
 
 @dataclass

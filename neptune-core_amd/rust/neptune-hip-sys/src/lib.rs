@@ -311,6 +311,86 @@ pub struct nhip_ms_updated {
     pub rel_words: usize,
 }
 
+/// Parameters of a block file's mutator-set and transaction rules (`nhip_blk_ms_check`): the two type-script
+/// digests (canonical), the pow tree height and the limits of rules 2.j-2.l.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct nhip_blk_ms_params {
+    pub native_currency_hash: [u64; 5],
+    pub time_lock_hash: [u64; 5],
+    pub pow_tree_height: u32,
+    pub max_num_inputs: u32,
+    pub max_num_outputs: u32,
+    pub max_num_announcements: u32,
+}
+
+/// What `nhip_blk_ms_walk` extracts of n scanned blocks (two-call sizing: every array pointer null writes the
+/// totals only).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct nhip_blk_ms_parts {
+    pub height: *mut u64,
+    pub timestamp: *mut u64,
+    pub receiver_digest: *mut u64,
+    pub lock_script_hash: *mut u64,
+    pub fee: *mut u64,
+    pub coinbase: *mut u64,
+    pub coinbase_tag: *mut u8,
+    pub kernel_timestamp: *mut u64,
+    pub n_announcements: *mut u64,
+    pub aocl_num_leafs: *mut u64,
+    pub swbf_num_leafs: *mut u64,
+    pub aocl_n_peaks: *mut u32,
+    pub swbf_n_peaks: *mut u32,
+    pub aocl_peaks: *mut u64,
+    pub swbf_peaks: *mut u64,
+    pub active_off: *mut u64,
+    pub active: *mut u32,
+    pub out_off: *mut u64,
+    pub outputs: *mut u64,
+    pub rec_off: *mut u64,
+    pub minimum: *mut u64,
+    pub distances: *mut u32,
+    pub entry_off: *mut u64,
+    pub chunk_index: *mut u64,
+    pub path_off: *mut u64,
+    pub path: *mut u64,
+    pub rel_off: *mut u64,
+    pub rel: *mut u32,
+    pub active_cap: usize,
+    pub outputs_cap: usize,
+    pub records_cap: usize,
+    pub entries_cap: usize,
+    pub path_cap: usize,
+    pub rel_cap: usize,
+    pub active_words: usize,
+    pub n_outputs: usize,
+    pub records: usize,
+    pub entries: usize,
+    pub path_digests: usize,
+    pub rel_words: usize,
+}
+
+pub const NHIP_GUESSER_OK: u8 = 0;
+pub const NHIP_GUESSER_NEGATIVE_FEE: u8 = 1;
+
+pub const NHIP_BLKMS_OK: u8 = 0;
+pub const NHIP_BLKMS_SKIPPED: u8 = 1;
+pub const NHIP_BLKMS_UNPACK: u8 = 2;
+pub const NHIP_BLKMS_PARENT_NEGATIVE_FEE: u8 = 3;
+pub const NHIP_BLKMS_PARENT_MSA_INCONSISTENT: u8 = 4;
+pub const NHIP_BLKMS_REMOVAL_RECORDS_VALIDITY: u8 = 5;
+pub const NHIP_BLKMS_REMOVAL_RECORDS_UNIQUENESS: u8 = 6;
+pub const NHIP_BLKMS_UPDATE_IMPOSSIBLE: u8 = 7;
+pub const NHIP_BLKMS_UPDATE_INTEGRITY: u8 = 8;
+pub const NHIP_BLKMS_TRANSACTION_TIMESTAMP: u8 = 9;
+pub const NHIP_BLKMS_COINBASE_TOO_BIG: u8 = 10;
+pub const NHIP_BLKMS_NEGATIVE_COINBASE: u8 = 11;
+pub const NHIP_BLKMS_NEGATIVE_FEE: u8 = 12;
+pub const NHIP_BLKMS_TOO_MANY_INPUTS: u8 = 13;
+pub const NHIP_BLKMS_TOO_MANY_OUTPUTS: u8 = 14;
+pub const NHIP_BLKMS_TOO_MANY_ANNOUNCEMENTS: u8 = 15;
+
 /// Statuses and the unpacked dictionaries of `nhip_ms_unpack_plan` / `nhip_ms_unpack_batch` (two-call sizing:
 /// every array pointer but `status` and `num_leafs_aocl` null writes the totals only).
 #[repr(C)]
@@ -578,6 +658,16 @@ extern "C" {
                                out: *mut nhip_ms_updated) -> c_int;
     pub fn nhip_ms_update_batch(ctx: *mut nhip_ctx, block: *const nhip_ms_apply_in, block_out: *mut nhip_ms_apply_out,
                                 wit: *const nhip_ms_update_in, out: *mut nhip_ms_updated) -> c_int;
+    pub fn nhip_blk_ms_params_default(out: *mut nhip_blk_ms_params);
+    pub fn nhip_blk_ms_walk(bytes: *const u8, n_bytes: usize, pow_tree_height: u32, blocks: *const nhip_blk_block,
+                            n: usize, out: *mut nhip_blk_ms_parts) -> c_int;
+    pub fn nhip_blk_guesser_fee_records(ctx: *mut nhip_ctx, bytes: *const u8, n_bytes: usize,
+                                        params: *const nhip_blk_ms_params, blocks: *const nhip_blk_block, n: usize,
+                                        digests: *const u64, records: *mut u64, n_records: *mut u8,
+                                        status: *mut u8) -> c_int;
+    pub fn nhip_blk_ms_check(ctx: *mut nhip_ctx, bytes: *const u8, n_bytes: usize, params: *const nhip_blk_ms_params,
+                             blocks: *const nhip_blk_block, n: usize, parent_of: *const i64, digests: *const u64,
+                             status: *mut u8, ms_status: *mut u8, bad_record: *mut u64) -> c_int;
     pub fn nhip_timing_enable(ctx: *mut nhip_ctx, on: c_int) -> c_int;
     pub fn nhip_timing_read(ctx: *mut nhip_ctx, total_ms: *mut f64, launches: *mut u64, reset: c_int) -> c_int;
 }
