@@ -907,6 +907,50 @@ int nhip_ms_update_plan(const nhip_ms_apply_in *block, const nhip_ms_update_in *
 int nhip_ms_update_batch(nhip_ctx *ctx, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out,
                          const nhip_ms_update_in *wit, nhip_ms_updated *out);
 
+/* ---- witnesses resident on the device across blocks -----------------------------
+ * A store owns the witnesses of nhip_ms_update_batch (same description: nhip_ms_update_in) in device memory of
+ * its own and brings all of them across one block per nhip_ms_store_update: §6g for one job, its witness side
+ * bound to the store.  Only the block, the plan's integer arrays, block_out and one status byte per witness cross
+ * to or from the host; no path digest and no chunk word of a witness does after nhip_ms_store_append.  The host
+ * keeps a mirror of the integers alone (index sets, leaf indices, the four offset arrays, the keys).
+ * Witnesses are numbered 0 .. W-1 in insertion order; the positions are stable until nhip_ms_store_retain.
+ * A store belongs to one nhip_ctx (which must outlive it) and to one tip; calls on it are serialized by the
+ * context.  Status rules beyond nhip_ms_update_batch's, all failing closed:
+ *   - unless the block ends NHIP_MS_OK the store is unchanged and every returned status is NHIP_MS_JOB_REJECTED;
+ *   - NHIP_ERR_HIP / NHIP_ERR_OOM / NHIP_ERR_ARG leave the store unchanged;
+ *   - a witness whose status after an update is not NHIP_MS_OK keeps its position and its planned slots, zero-filled
+ *     (keys included); the status is sticky: every later update, read and check reports that first status, the slots
+ *     stay zero and are planned by shape like any other's, until nhip_ms_store_retain drops the witness.
+ * The gather kernel behind read and retain works in units of NHIP_MS_STORE_GATHER_UNIT 8-byte destination words
+ * (twice as many u32 chunk words). */
+#define NHIP_MS_STORE_GATHER_UNIT 1024
+typedef struct nhip_ms_store nhip_ms_store;
+/* initial capacities (0: a default); every capacity grows geometrically on demand, device to device */
+typedef struct {
+    size_t witnesses, aocl_digests, entries, path_digests, rel_words;
+} nhip_ms_store_caps;
+int nhip_ms_store_create(nhip_ctx *ctx, const nhip_ms_store_caps *initial, nhip_ms_store **out);
+void nhip_ms_store_destroy(nhip_ms_store *store);
+/* the totals, from the host mirror; any pointer may be NULL */
+int nhip_ms_store_count(const nhip_ms_store *store, uint64_t *witnesses, uint64_t *aocl_digests, uint64_t *entries,
+                        uint64_t *path_digests, uint64_t *rel_words);
+/* n witnesses behind the existing ones (wit->wit_off is ignored); the shape checks of nhip_ms_update_batch */
+int nhip_ms_store_append(nhip_ms_store *store, const nhip_ms_update_in *wit, size_t n);
+/* block->n_jobs == 1; block_out as nhip_ms_apply_batch fills it; status: W bytes, or NULL */
+int nhip_ms_store_update(nhip_ms_store *store, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out,
+                         uint8_t *status);
+/* The witnesses sel[0 .. n_sel) (any order, repeats allowed; sel == NULL with n_sel == W: all) in the layout of
+ * nhip_ms_updated, with its two-call sizing; the count pass reads the mirror alone.  An index >= W is
+ * NHIP_ERR_ARG with the outputs untouched.  One gather on the device, then one copy per array. */
+int nhip_ms_store_read(nhip_ms_store *store, const uint64_t *sel, size_t n_sel, nhip_ms_updated *out);
+/* keep: W bytes; the witnesses with keep[i] != 0 stay, in order */
+int nhip_ms_store_retain(nhip_ms_store *store, const uint8_t *keep);
+/* Per witness against msa, W bytes each: aocl_member = MmrMembershipProof::verify of its leaf under msa->aocl (1
+ * for a removal record); valid / can_remove / status as nhip_ms_can_remove_batch decides its index set and
+ * dictionary.  A sticky witness reports its sticky status and zeros.  Nothing of the store moves. */
+int nhip_ms_store_check(nhip_ms_store *store, const nhip_msa *msa, uint8_t *aocl_member, uint8_t *valid,
+                        uint8_t *can_remove, uint8_t *status);
+
 /* ---- a block file's mutator-set and transaction rules ---------------------------
  * Block::validate rules 2.a-2.l (protocol/consensus/block/mod.rs:811-891) for every (parent, child) pair of
  * scanned blocks, from the file's bytes: msa_before is the parent's Block::mutator_set_accumulator_after

@@ -139,6 +139,39 @@ hipError_t launch_ms_wit_paths(const MsApplyDev& a, const MsUpdateDev& u, size_t
 hipError_t launch_ms_wit_chunks(const MsApplyDev& a, const MsUpdateDev& u, size_t entries, hipStream_t st);
 hipError_t launch_ms_wit_seal(const MsUpdateDev& u, size_t witnesses, hipStream_t st);
 
+// ---- the device-resident witness store (ms_store_kernels.hip); every pointer a device pointer
+// A selection (MsStoreSelect, ms_store.hpp) and the pools it is gathered from and into.  Pools: 0 AOCL path digests,
+// 1 keys, 2 dictionary path digests, 3 chunk words.  The d_* fixed arrays may be null together (read: none is copied).
+struct MsStoreGatherDev {
+    size_t n;                // selected witnesses
+    const uint64_t* sel;     // n (read by the fixed part only)
+    const uint64_t* src[4];  // n: the begin of each witness's range in the source pool
+    const uint64_t* dst[4];  // n + 1: the exclusive scan of the selected lengths
+    const uint32_t* unit_first;  // MsStoreSelect::unit_first
+    const uint64_t *s_aocl, *s_key, *s_path;
+    const uint32_t* s_rel;
+    uint64_t *d_aocl, *d_key, *d_path;
+    uint32_t* d_rel;
+    const uint64_t *s_minimum, *s_leaf_index, *s_leaf;
+    const uint32_t* s_distances;
+    const uint8_t* s_sticky;
+    uint64_t *d_minimum, *d_leaf_index, *d_leaf;
+    uint32_t* d_distances;
+    uint8_t* d_sticky;
+};
+// the work units of one gather: pool p has the units [end[p - 1], end[p]), the fixed part [end[3], end[4])
+struct MsStoreGatherUnits {
+    uint64_t end[5];
+};
+// unit_end: MsStoreSelect::unit_end
+MsStoreGatherUnits ms_store_gather_units(const uint64_t unit_end[4], size_t n, bool fixed);
+hipError_t launch_ms_store_gather(const MsStoreGatherDev& g, const MsStoreGatherUnits& units, hipStream_t st);
+hipError_t launch_ms_store_seal(const MsUpdateDev& u, const uint8_t* sticky, uint8_t* sticky_next, size_t witnesses,
+                                hipStream_t st);
+hipError_t launch_ms_store_check_seal(const uint64_t* d_leaf_index, const uint8_t* d_sticky, size_t witnesses,
+                                      uint8_t* d_member, uint8_t* d_valid, uint8_t* d_verdict, uint8_t* d_status,
+                                      hipStream_t st);
+
 // ---- packed removal records (ms_unpack_kernels.hip); every pointer a device pointer
 // The program of MsUnpackPlan (ms_unpack_plan.hpp) and the buffers it runs over.
 struct MsUnpackDev {

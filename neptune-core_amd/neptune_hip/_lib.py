@@ -184,6 +184,15 @@ class MsUpdated(ctypes.Structure):
                 ("path_digests", ctypes.c_size_t), ("rel_words", ctypes.c_size_t)]
 
 
+class MsStoreCaps(ctypes.Structure):
+    """nhip_ms_store_caps: the initial capacities of a witness store (0: a default)."""
+    _fields_ = [("witnesses", ctypes.c_size_t), ("aocl_digests", ctypes.c_size_t), ("entries", ctypes.c_size_t),
+                ("path_digests", ctypes.c_size_t), ("rel_words", ctypes.c_size_t)]
+
+
+MS_STORE_GATHER_UNIT = 1024  # NHIP_MS_STORE_GATHER_UNIT: 8-byte destination words per work unit of the gather
+
+
 class BlkMsParams(ctypes.Structure):
     """nhip_blk_ms_params: the type-script digests, the pow tree height and the limits of rules 2.j-2.l."""
     _fields_ = [("native_currency_hash", ctypes.c_uint64 * 5), ("time_lock_hash", ctypes.c_uint64 * 5),
@@ -354,6 +363,14 @@ SIGNATURES = {
                                 ctypes.c_int),
     "nhip_blk_digests": ([_vp, _vp, _sz, ctypes.c_uint32, _vp, _sz, _vp, _vp], ctypes.c_int),
     "nhip_blk_chain_check": ([_vp, _vp, _sz, ctypes.POINTER(ChainParams), _vp, _sz, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "nhip_ms_store_create": ([_vp, ctypes.POINTER(MsStoreCaps), ctypes.POINTER(_vp)], ctypes.c_int),
+    "nhip_ms_store_destroy": ([_vp], None),
+    "nhip_ms_store_count": ([_vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "nhip_ms_store_append": ([_vp, ctypes.POINTER(MsUpdateIn), _sz], ctypes.c_int),
+    "nhip_ms_store_update": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut), _vp], ctypes.c_int),
+    "nhip_ms_store_read": ([_vp, _vp, _sz, ctypes.POINTER(MsUpdated)], ctypes.c_int),
+    "nhip_ms_store_retain": ([_vp, _vp], ctypes.c_int),
+    "nhip_ms_store_check": ([_vp, ctypes.POINTER(Msa), _vp, _vp, _vp, _vp], ctypes.c_int),
     "nhip_blk_ms_params_default": ([ctypes.POINTER(BlkMsParams)], None),
     "nhip_blk_ms_walk": ([_vp, _sz, ctypes.c_uint32, _vp, _sz, ctypes.POINTER(BlkMsParts)], ctypes.c_int),
     "nhip_blk_guesser_fee_records": ([_vp, _vp, _sz, ctypes.POINTER(BlkMsParams), _vp, _sz, _vp, _vp, _vp, _vp],

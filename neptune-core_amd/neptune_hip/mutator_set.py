@@ -537,3 +537,135 @@ def update_removal_records(ctx, msa_before: MutatorSetAccumulator, update: Mutat
     wits = [Witness(r.absolute_indices, list(r.target_chunks)) for r in records]
     _, status, _, after, ws = update_witnesses_batch(ctx, [(msa_before, update, wits)])[0]
     return status, after, [(st, None if w is None else RemovalRecord(w.absolute_indices, w.target_chunks)) for st, w in ws]
+
+
+# ---------------------------------------------------------------- witnesses resident on the device
+class PackedWitnesses:
+    """The witness half of `PackedUpdate` alone: `win` is the `nhip_ms_update_in` of `witnesses` as one job."""
+
+    def __init__(self, witnesses):
+        wits = self.witnesses = list(witnesses)
+        W = self.n = len(wits)
+        self.wit_off = _csr([W])
+        self.minimum, self.distances = _index_arrays(wits)
+        self.leaf_index = np.asarray([2 ** 64 - 1 if w.aocl_leaf_index is None else int(w.aocl_leaf_index) for w in wits],
+                                     dtype=np.uint64)
+        self.leaf = np.zeros((W, 5), dtype=np.uint64)
+        for i, w in enumerate(wits):
+            if w.aocl_leaf_index is not None:
+                self.leaf[i] = np.asarray([int(x) for x in w.aocl_leaf], dtype=np.uint64)
+        self.aocl_path_off, self.aocl_path = pack_paths([w.auth_path_aocl for w in wits])
+        self.packed = pack_chunks(wits)
+        self.chunks = self.packed._c()
+        self.win = _lib.MsUpdateIn(self.wit_off.ctypes.data, _ptr(self.minimum), _ptr(self.distances),
+                                   _ptr(self.leaf_index), _ptr(self.leaf), self.aocl_path_off.ctypes.data,
+                                   _ptr(self.aocl_path), ctypes.pointer(self.chunks))
+
+
+class WitnessStore:
+    """Membership proofs and removal records kept on the device across blocks (`nhip_ms_store_*`): `append` uploads
+    witnesses once, `update` brings all of them across one block where they lie (only the block goes up and one
+    status byte per witness comes back), `read` copies chosen ones out, `retain` drops the others, `check` answers
+    "which of them verify / can still be removed" against an accumulator.  Witnesses keep their positions
+    `0 .. len - 1` in insertion order until `retain`.  A witness whose status after an update is not OK keeps that
+    status (and zeroed slots) until `retain` drops it.  `initial`: a dict of initial capacities (`witnesses`,
+    `aocl_digests`, `entries`, `path_digests`, `rel_words`), or None."""
+
+    def __init__(self, ctx, initial=None):
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        caps = _lib.MsStoreCaps(**initial) if initial else None
+        check(ctx.lib.nhip_ms_store_create(ctx.handle, ctypes.byref(caps) if caps else None, ctypes.byref(self._h)),
+              "nhip_ms_store_create")
+        self._fixed = []  # per witness: (index set, leaf index, leaf), which no block changes
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.nhip_ms_store_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return len(self._fixed)
+
+    def counts(self):
+        """`(witnesses, aocl_digests, entries, path_digests, rel_words)` from the host mirror."""
+        c = (ctypes.c_uint64 * 5)()
+        check(self.ctx.lib.nhip_ms_store_count(self._h, *(ctypes.addressof(c) + 8 * i for i in range(5))),
+              "nhip_ms_store_count")
+        return tuple(int(x) for x in c)
+
+    def append(self, witnesses):
+        pw = PackedWitnesses(witnesses)
+        check(self.ctx.lib.nhip_ms_store_append(self._h, ctypes.byref(pw.win), pw.n), "nhip_ms_store_append")
+        self._fixed += [(w.absolute_indices, w.aocl_leaf_index, w.aocl_leaf) for w in pw.witnesses]
+
+    def update(self, msa_before, update, expected=None):
+        """One block: `((verdict, status, bad_record, msa_after), [status of every witness])`.  Unless the block's
+        status is OK the store is unchanged and every witness status is JOB_REJECTED."""
+        pa = PackedApply([(msa_before, update)], None if expected is None else [expected])
+        status = np.zeros(max(len(self), 1), dtype=np.uint8)
+        check(self.ctx.lib.nhip_ms_store_update(self._h, ctypes.byref(pa.cin), ctypes.byref(pa.cout), status.ctypes.data),
+              "nhip_ms_store_update")
+        return _apply_results(pa)[0], [int(x) for x in status[:len(self)]]
+
+    def read_raw(self, indices=None):
+        """Both calls of the two-call pattern: `(sel, count-pass totals, the output arrays)`."""
+        if indices is None:
+            sel, n = None, len(self)
+        else:
+            sel = np.ascontiguousarray(np.asarray(list(indices), dtype=np.uint64))
+            n = sel.size
+        cout = _lib.MsUpdated()
+        p_sel = None if sel is None else (sel.ctypes.data if n else None)
+        if sel is not None and n == 0:
+            p_sel = np.zeros(1, dtype=np.uint64).ctypes.data  # an empty selection, not "all"
+        check(self.ctx.lib.nhip_ms_store_read(self._h, p_sel, n, ctypes.byref(cout)), "nhip_ms_store_read")
+        totals = tuple(int(getattr(cout, f)) for f in ("aocl_digests", "entries", "path_digests", "rel_words"))
+        A, E, PD, RW = totals
+        z = lambda dtype, *shape: np.zeros(shape, dtype=dtype)  # noqa: E731
+        o = dict(status=z(np.uint8, n), aocl_path_off=z(np.uint64, n + 1), aocl_path=z(np.uint64, A, 5),
+                 entry_off=z(np.uint64, n + 1), chunk_index=z(np.uint64, E), path_off=z(np.uint64, E + 1),
+                 path=z(np.uint64, PD, 5), rel_off=z(np.uint64, E + 1), rel=z(np.uint32, RW))
+        pad = {f: (a if a.size else np.zeros(1, dtype=a.dtype)) for f, a in o.items()}
+        cout = _lib.MsUpdated(*(pad[f].ctypes.data for f, _ in _lib.MsUpdated._fields_[:9]), A, E, PD, RW)
+        check(self.ctx.lib.nhip_ms_store_read(self._h, p_sel, n, ctypes.byref(cout)), "nhip_ms_store_read")
+        filled = tuple(int(getattr(cout, f)) for f in ("aocl_digests", "entries", "path_digests", "rel_words"))
+        if filled != totals:
+            raise _lib.NhipError("nhip_ms_store_read: the count pass and the fill disagree")
+        return (list(range(n)) if sel is None else [int(x) for x in sel]), totals, o
+
+    def read(self, indices=None):
+        """`[(status, Witness)]` of the chosen witnesses (None: all), in the order asked; a witness whose status is
+        not OK comes with its zeroed slots."""
+        sel, _, o = self.read_raw(indices)
+        dictionaries = unpack_chunks(PackedChunks(o["entry_off"], o["chunk_index"], o["path_off"], o["path"],
+                                                  o["rel_off"], o["rel"]))
+        out = []
+        for i, w in enumerate(sel):
+            idx, leaf_index, leaf = self._fixed[w]
+            path = [tuple(int(x) for x in d) for d in o["aocl_path"][int(o["aocl_path_off"][i]):int(o["aocl_path_off"][i + 1])]]
+            out.append((int(o["status"][i]), Witness(idx, dictionaries[i], leaf_index, leaf, path)))
+        return out
+
+    def retain(self, mask):
+        mask = [bool(x) for x in mask]
+        if len(mask) != len(self):
+            raise ValueError("one flag per witness")
+        keep = np.asarray(mask, dtype=np.uint8)
+        check(self.ctx.lib.nhip_ms_store_retain(self._h, _ptr(keep)), "nhip_ms_store_retain")
+        self._fixed = [f for f, k in zip(self._fixed, mask) if k]
+
+    def check(self, msa):
+        """`[(aocl_member, valid, can_remove, status)]` of every witness against `msa`."""
+        n = len(self)
+        cm, _keep = msa._c()
+        a = [np.zeros(max(n, 1), dtype=np.uint8) for _ in range(4)]
+        check(self.ctx.lib.nhip_ms_store_check(self._h, ctypes.byref(cm), *(x.ctypes.data for x in a)),
+              "nhip_ms_store_check")
+        return [(bool(a[0][i]), bool(a[1][i]), bool(a[2][i]), int(a[3][i])) for i in range(n)]

@@ -30,7 +30,8 @@ pub const NHIP_HW_QUEUES_RECOMMENDED: u32 = 8;
 macro_rules! opaque {
     ($($name:ident),*) => { $( #[repr(C)] pub struct $name { _p: [u8; 0] } )* };
 }
-opaque!(nhip_ctx, nhip_air, nhip_batch, nhip_group, nhip_group_stream, nhip_queue, nhip_pow_buffer, nhip_arena);
+opaque!(nhip_ctx, nhip_air, nhip_batch, nhip_group, nhip_group_stream, nhip_queue, nhip_pow_buffer, nhip_arena,
+        nhip_ms_store);
 
 /// `Stark::default()` plus the table dimensions (`nhip_stark_params_default`).
 #[repr(C)]
@@ -305,6 +306,20 @@ pub struct nhip_ms_updated {
     pub entries_cap: usize,
     pub path_cap: usize,
     pub rel_cap: usize,
+    pub aocl_digests: usize,
+    pub entries: usize,
+    pub path_digests: usize,
+    pub rel_words: usize,
+}
+
+/// 8-byte destination words per work unit of the store's gather kernel (`NHIP_MS_STORE_GATHER_UNIT`).
+pub const NHIP_MS_STORE_GATHER_UNIT: usize = 1024;
+
+/// Initial capacities of a device-resident witness store (`nhip_ms_store_create`; 0: a default).
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct nhip_ms_store_caps {
+    pub witnesses: usize,
     pub aocl_digests: usize,
     pub entries: usize,
     pub path_digests: usize,
@@ -658,6 +673,19 @@ extern "C" {
                                out: *mut nhip_ms_updated) -> c_int;
     pub fn nhip_ms_update_batch(ctx: *mut nhip_ctx, block: *const nhip_ms_apply_in, block_out: *mut nhip_ms_apply_out,
                                 wit: *const nhip_ms_update_in, out: *mut nhip_ms_updated) -> c_int;
+    pub fn nhip_ms_store_create(ctx: *mut nhip_ctx, initial: *const nhip_ms_store_caps,
+                                out: *mut *mut nhip_ms_store) -> c_int;
+    pub fn nhip_ms_store_destroy(store: *mut nhip_ms_store);
+    pub fn nhip_ms_store_count(store: *const nhip_ms_store, witnesses: *mut u64, aocl_digests: *mut u64,
+                               entries: *mut u64, path_digests: *mut u64, rel_words: *mut u64) -> c_int;
+    pub fn nhip_ms_store_append(store: *mut nhip_ms_store, wit: *const nhip_ms_update_in, n: usize) -> c_int;
+    pub fn nhip_ms_store_update(store: *mut nhip_ms_store, block: *const nhip_ms_apply_in,
+                                block_out: *mut nhip_ms_apply_out, status: *mut u8) -> c_int;
+    pub fn nhip_ms_store_read(store: *mut nhip_ms_store, sel: *const u64, n_sel: usize,
+                              out: *mut nhip_ms_updated) -> c_int;
+    pub fn nhip_ms_store_retain(store: *mut nhip_ms_store, keep: *const u8) -> c_int;
+    pub fn nhip_ms_store_check(store: *mut nhip_ms_store, msa: *const nhip_msa, aocl_member: *mut u8, valid: *mut u8,
+                               can_remove: *mut u8, status: *mut u8) -> c_int;
     pub fn nhip_blk_ms_params_default(out: *mut nhip_blk_ms_params);
     pub fn nhip_blk_ms_walk(bytes: *const u8, n_bytes: usize, pow_tree_height: u32, blocks: *const nhip_blk_block,
                             n: usize, out: *mut nhip_blk_ms_parts) -> c_int;
