@@ -907,6 +907,47 @@ int nhip_ms_update_plan(const nhip_ms_apply_in *block, const nhip_ms_update_in *
 int nhip_ms_update_batch(nhip_ctx *ctx, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out,
                          const nhip_ms_update_in *wit, nhip_ms_updated *out);
 
+/* ---- membership proofs and removal records back across a block -----------------
+ * MsMembershipProof::revert_update_from_remove / revert_update_from_batch_addition
+ * (ms_membership_proof.rs:380-413, 517-557; shared.rs:154-224) over a whole block, as a reorganisation walks the
+ * abandoned blocks backwards (state/mod.rs:1392-1497), computed as the end state.  A job is a job of
+ * nhip_ms_apply_batch: msa_before, the block's addition records and its removal records as the block carries them
+ * (valid against msa_before), optionally msa_expected, the accumulator the witnesses stand at.  The witnesses (the
+ * structs of nhip_ms_update_batch) stand at the accumulator *after* the job and are taken to msa_before.  With
+ * n0 / n1 the AOCL leaf counts before / after and b0 / b1 the batch indices before / after:
+ *   job:       steps 1-5 of nhip_ms_apply_batch; unless the job ends NHIP_MS_OK every witness of it gets
+ *              NHIP_MS_JOB_REJECTED.  With msa_expected rule 2.e checks that this block led to that accumulator.
+ *   admission: per witness as it stands after the block, integer and word comparisons only, the first failure of
+ *              NHIP_MS_NOT_IN_AOCL   (AOCL part only) l >= n0 (born in this block or later: the reference asserts,
+ *                                    ms_membership_proof.rs:386-389), or the path has not ilog2(l ^ n1) digests;
+ *              NHIP_MS_OUT_OF_RANGE  minimum + distance saturates u128, or a chunk index exceeds b1 + 255;
+ *              NHIP_MS_ABSENT_CHUNK  the dictionary's keys are not, strictly ascending, exactly the witness's
+ *                                    chunk indices below b1;
+ *              NHIP_MS_BAD_MMR_PATH  an entry's path has not ilog2(key ^ b1) digests, or (decided on the device) a
+ *                                    kept entry's chunk holds fewer copies of a block index than the block inserted.
+ *   before:    the AOCL path keeps its first ilog2(l ^ n0) digests; the dictionary keeps the entries with key < b0,
+ *              in order (the chunks b0 .. b1 - 1 were still in the window); a kept chunk loses one copy of each of
+ *              the block's indices in it per occurrence (Chunk::remove_once); a kept path keeps its first
+ *              ilog2(key ^ b0) digests, and digest t becomes the old value of node (t, (key >> t) ^ 1) where that
+ *              node is a chunk a block record touches or an ancestor of one, else stays.  The old values come from
+ *              the block's records alone: a record's entry holds the chunk and its path before the block.
+ *   verified:  every reverted witness is authenticated against msa_before where it was written, the only
+ *              cryptographic check and a complete one (the reference's assert after each reverted block): its leaf
+ *              under msa_before.aocl, else NHIP_MS_NOT_IN_AOCL; every entry under msa_before.swbf_inactive, else
+ *              NHIP_MS_BAD_MMR_PATH.  Whatever a revert returns NHIP_MS_OK is valid against msa_before, stale or
+ *              forged input included.
+ * NHIP_MS_UPDATE_INTERNAL keeps its meaning.  Output lengths are integers of the inputs (a kept chunk: its length
+ * less the block's indices in that chunk, floored at 0), laid out by nhip_ms_revert_plan as if every job and witness
+ * were accepted; a failed witness keeps its planned slots zero-filled, keys included.  Two-call sizing as
+ * nhip_ms_update_plan.
+ * One divergence fails open only by construction of the input: a removal record has no leaf index, so one whose
+ * item was born in the reverted block cannot be recognised as such.  It is reverted by shape and passes or fails the
+ * verification like any other; the caller drops the mempool transactions of the abandoned fork. */
+int nhip_ms_revert_plan(const nhip_ms_apply_in *block, const nhip_ms_update_in *wit, nhip_ms_updated *out);
+/* block_out is filled as nhip_ms_apply_batch fills it.  Shape errors are NHIP_ERR_ARG with the outputs untouched. */
+int nhip_ms_revert_batch(nhip_ctx *ctx, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out,
+                         const nhip_ms_update_in *wit, nhip_ms_updated *out);
+
 /* ---- witnesses resident on the device across blocks -----------------------------
  * A store owns the witnesses of nhip_ms_update_batch (same description: nhip_ms_update_in) in device memory of
  * its own and brings all of them across one block per nhip_ms_store_update: §6g for one job, its witness side
@@ -938,6 +979,15 @@ int nhip_ms_store_count(const nhip_ms_store *store, uint64_t *witnesses, uint64_
 int nhip_ms_store_append(nhip_ms_store *store, const nhip_ms_update_in *wit, size_t n);
 /* block->n_jobs == 1; block_out as nhip_ms_apply_batch fills it; status: W bytes, or NULL */
 int nhip_ms_store_update(nhip_ms_store *store, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out,
+                         uint8_t *status);
+/* The way back when the tip moves to another fork: nhip_ms_revert_batch for one job, its witness side bound to the
+ * store, which stands at the accumulator after `block` and is taken to block->msa_before.  A caller who passes the
+ * store's tip as msa_expected gets rule 2.e as the check that this block led to that tip.  The contract of
+ * nhip_ms_store_update: unless the block ends NHIP_MS_OK the store is unchanged byte for byte and every status is
+ * NHIP_MS_JOB_REJECTED; HIP, OOM and ARG errors leave it unchanged; sticky statuses carry over and new failures (a
+ * witness born in the reverted block among them) become sticky; only the block, the plan's integer arrays, block_out
+ * and W status bytes cross to or from the host. */
+int nhip_ms_store_revert(nhip_ms_store *store, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out,
                          uint8_t *status);
 /* The witnesses sel[0 .. n_sel) (any order, repeats allowed; sel == NULL with n_sel == W: all) in the layout of
  * nhip_ms_updated, with its two-call sizing; the count pass reads the mirror alone.  An index >= W is

@@ -139,6 +139,24 @@ hipError_t launch_ms_wit_paths(const MsApplyDev& a, const MsUpdateDev& u, size_t
 hipError_t launch_ms_wit_chunks(const MsApplyDev& a, const MsUpdateDev& u, size_t entries, hipStream_t st);
 hipError_t launch_ms_wit_seal(const MsUpdateDev& u, size_t witnesses, hipStream_t st);
 
+// ---- witnesses back across a block (ms_revert_kernels.hip); every pointer a device pointer
+// The kernels read an MsUpdateDev whose inputs are the witnesses after the block and whose plan is
+// ms_revert_plan's (auth stays null: no input entry is authenticated), the block's MsApplyDev behind k_ms_apply, and:
+struct MsRevertDev {
+    const uint64_t* node_off;  // per job, in digests: ms_revert_node_offsets
+    uint64_t* nodes;           // the old levels of the touched chunks: level L of group g at node_off[j] + L n_grp + g
+    uint8_t* short_of;         // per witness: a kept chunk holds fewer copies of a block index than the block inserted
+    const uint8_t* member;     // per witness, from k_ms_rev_aocl_jobs over the reverted AOCL parts
+    const uint8_t* auth;       // per output entry, from k_ms_chunk_auth_jobs over the reverted dictionaries
+};
+hipError_t launch_ms_revert_nodes(const MsApplyDev& a, const MsRevertDev& r, size_t n_jobs, size_t groups, hipStream_t st);
+hipError_t launch_ms_rev_admit(const MsApplyDev& a, const MsUpdateDev& u, const MsRevertDev& r, size_t witnesses, hipStream_t st);
+hipError_t launch_ms_rev_paths(const MsApplyDev& a, const MsUpdateDev& u, const MsRevertDev& r, size_t witnesses,
+                               size_t entries, hipStream_t st);
+hipError_t launch_ms_rev_chunks(const MsApplyDev& a, const MsUpdateDev& u, const MsRevertDev& r, size_t entries, hipStream_t st);
+hipError_t launch_ms_rev_aocl_jobs(const MsApplyDev& a, const MsUpdateDev& u, uint8_t* d_member, size_t witnesses, hipStream_t st);
+hipError_t launch_ms_rev_seal(const MsUpdateDev& u, const MsRevertDev& r, size_t witnesses, hipStream_t st);
+
 // ---- the device-resident witness store (ms_store_kernels.hip); every pointer a device pointer
 // A selection (MsStoreSelect, ms_store.hpp) and the pools it is gathered from and into.  Pools: 0 AOCL path digests,
 // 1 keys, 2 dictionary path digests, 3 chunk words.  The d_* fixed arrays may be null together (read: none is copied).

@@ -1,5 +1,5 @@
 // C-ABI layer of libneptune_hip.so, the mutator-set entry points (declarations: include/neptune_hip.h;
-// DESIGN.md §6c-§6g).  Each is: validate shapes, stage order (both ms_shape.cpp), build its parts, one Stage
+// DESIGN.md §6c-§6g, §6j).  Each is: validate shapes, stage order (both ms_shape.cpp), build its parts, one Stage
 // (ctx.hpp: declare the device buffers, commit, launch, read back), write the outputs.
 #include <hip/hip_runtime.h>
 
@@ -179,6 +179,33 @@ int nhip_ms_update_batch(nhip_ctx* c, const nhip_ms_apply_in* block, nhip_ms_app
         BlockPart blk(*block, *block_out, cnt, true);  // k_ms_apply keeps its nodes
         WitnessPart wp(*wit, wc, plan, *out);
         return run_parts(c, blk, &wp);
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// MsMembershipProof::revert_update_from_remove / revert_update_from_batch_addition over whole blocks, as the end
+// state: nhip_ms_apply_batch, then k_ms_revert_nodes, k_ms_rev_admit, k_ms_rev_paths, k_ms_rev_chunks,
+// the verification of every reverted witness against msa_before (k_ms_rev_aocl_jobs, k_ms_chunk_auth_jobs) and
+// k_ms_rev_seal.  The host lays out shapes only.  The block part does not keep its nodes: they are the values after
+// the block, and the revert reads the old ones, which k_ms_revert_nodes computes from the records.
+int nhip_ms_revert_batch(nhip_ctx* c, const nhip_ms_apply_in* block, nhip_ms_apply_out* block_out,
+                         const nhip_ms_update_in* wit, nhip_ms_updated* out) {
+    nhip::MsApplyCounts cnt;
+    nhip::MsUpdateCounts wc;
+    if (!c || !out || nhip::ms_apply_ok(block, block_out, &cnt) || nhip::ms_update_ok(block, wit, &wc)) return NHIP_ERR_ARG;
+    try {
+        nhip::MsUpdatePlan plan;
+        int rc = nhip::ms_revert_plan(block, wit, wc, &plan);
+        if (rc != NHIP_OK) return rc;
+        if ((rc = nhip::ms_updated_check(plan, true, out)) != NHIP_OK) return rc;
+        if (nhip::ms_updated_is_count_pass(out) || block->n_jobs == 0) {
+            nhip::ms_updated_write(plan, true, out);
+            return NHIP_OK;
+        }
+        BlockPart blk(*block, *block_out, cnt, false);
+        RevertPart rp(*wit, wc, plan, *out, blk);
+        return run_parts(c, blk, &rp);
     } catch (const std::bad_alloc&) {
         return NHIP_ERR_OOM;
     }

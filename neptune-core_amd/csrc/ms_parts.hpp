@@ -1,4 +1,4 @@
-// The parts a mutator-set entry point is built from (ms_capi.hip, ms_store_capi.hip; DESIGN.md §6d-§6i): each
+// The parts a mutator-set entry point is built from (ms_capi.hip, ms_store_capi.hip; DESIGN.md §6d-§6j): each
 // declares its device buffers on a Stage (ctx.hpp), enqueues its launches after commit(), reads back and writes the
 // caller's outputs once the whole call has succeeded.  Included by the .hip files of the entry points only.
 #pragma once
@@ -11,6 +11,7 @@
 #include "ctx.hpp"
 #include "kernels.hpp"
 #include "ms_shape.hpp"
+#include "ms_revert_plan.hpp"
 #include "ms_update_plan.hpp"
 
 using nhip::Stage;
@@ -170,29 +171,45 @@ struct WitnessResident {
     uint8_t* sticky_next;
 };
 
-// The witnesses' part of nhip_ms_update_batch (DESIGN.md §6g), behind a BlockPart that keeps its nodes: inputs that
-// passed ms_update_ok, the host plan, and an output that passed ms_updated_check for a fill.  With `resident`
-// (nhip_ms_store_update) the witnesses and the outputs are the store's device buffers: only the plan's arrays are
-// staged, only the statuses are read back (into `status_out`), and k_ms_store_seal runs behind k_ms_wit_seal.
-struct WitnessPart {
+// What the witness parts of an update and of a revert share: the witnesses as the caller or the store holds them, the
+// host plan (an MsUpdatePlan either way), the outputs, and the resident mode.  With `resident` (nhip_ms_store_update,
+// nhip_ms_store_revert) the witnesses and the outputs are the store's device buffers: only the plan's arrays are
+// staged, only the statuses are read back, and k_ms_store_seal runs behind the part's own seal.
+struct WitnessIO {
     const nhip_ms_update_in& wi;
     const nhip::MsUpdateCounts& counts;
     const nhip::MsUpdatePlan& up;
     nhip_ms_updated& out;
     const size_t W, WE, WA, OE, OPD, ORW;  // witnesses, their input entries, and the plan's output totals
     nhip::MsUpdateDev ud{};
-    const uint32_t* d_in_ent_wit = nullptr;  // per input entry: its witness
-    uint8_t* d_wauth = nullptr;
     std::vector<uint8_t> wstatus;  // a temporary, as BlockPart's
     const WitnessResident* const resident;
 
-    WitnessPart(const nhip_ms_update_in& wit, const nhip::MsUpdateCounts& wc, const nhip::MsUpdatePlan& plan,
-                nhip_ms_updated& out_, const WitnessResident* res = nullptr)
+    WitnessIO(const nhip_ms_update_in& wit, const nhip::MsUpdateCounts& wc, const nhip::MsUpdatePlan& plan,
+              nhip_ms_updated& out_, const WitnessResident* res)
         : wi(wit), counts(wc), up(plan), out(out_), W((size_t)wc.witnesses), WE((size_t)wc.chunks.entries),
           WA((size_t)plan.aocl_path_off[W]), OE(plan.chunk_index.size()), OPD((size_t)plan.path_off[OE]),
           ORW((size_t)plan.rel_off[OE]), wstatus(W), resident(res) {}
-    void declare(Stage& st) {
-        if (resident) return declare_resident(st);
+    // the witnesses, the plan and the outputs; status_bytes: per witness, the status first
+    void declare_io(Stage& st, size_t status_bytes) {
+        if (resident) {  // the plan's call-only arrays and the scratch; everything else is where the store keeps it
+            const WitnessResident& r = *resident;
+            ud = r.in;
+            ud.o_aocl_path_off = r.o_aocl_path_off;
+            ud.o_entry_off = r.o_entry_off;
+            ud.o_path_off = r.o_path_off;
+            ud.o_rel_off = r.o_rel_off;
+            ud.o_aocl_path = r.out.o_aocl_path;
+            ud.o_chunk_index = r.out.o_chunk_index;
+            ud.o_path = r.out.o_path;
+            ud.o_rel = r.out.o_rel;
+            st.in(ud.wit_job, up.wit_job.data(), W);
+            st.in(ud.o_key, up.chunk_index.data(), OE);  // the plan's keys; the store's are the device's (o_chunk_index)
+            st.in(ud.o_ent_wit, up.ent_wit.data(), OE);
+            st.in(ud.o_ent_src, up.ent_src.data(), OE);
+            st.tmp(ud.status, W, status_bytes);
+            return;
+        }
         st.in(ud.minimum, wi.minimum, W, 2);
         st.in(ud.distances, wi.distances, W, 45);
         st.in(ud.aocl_leaf_index, wi.aocl_leaf_index, W);
@@ -201,7 +218,6 @@ struct WitnessPart {
         st.in(ud.aocl_path, wi.aocl_path, (size_t)counts.aocl_digests, 5);
         stage_chunks(st, W ? *wi.chunks : NO_CHUNKS, W, counts.chunks, ud.ch);
         st.in(ud.wit_job, up.wit_job.data(), W);
-        st.in(d_in_ent_wit, up.in_ent_wit.data(), WE);
         st.in(ud.o_aocl_path_off, up.aocl_path_off.data(), W + 1);
         st.in(ud.o_entry_off, up.entry_off.data(), W + 1);
         st.in(ud.o_key, up.chunk_index.data(), OE);
@@ -209,50 +225,22 @@ struct WitnessPart {
         st.in(ud.o_rel_off, up.rel_off.data(), OE + 1);
         st.in(ud.o_ent_wit, up.ent_wit.data(), OE);
         st.in(ud.o_ent_src, up.ent_src.data(), OE);
-        st.tmp(d_wauth, WE);
-        st.tmp(ud.status, W, 2);  // per witness: status, error byte
+        st.tmp(ud.status, W, status_bytes);
         st.tmp(ud.o_aocl_path, WA, 5);
         st.tmp(ud.o_chunk_index, OE);
         st.tmp(ud.o_path, OPD, 5);
         st.tmp(ud.o_rel, ORW);
     }
-    // the plan's call-only arrays and the scratch; everything else is where the store keeps it
-    void declare_resident(Stage& st) {
+    // after commit(), resident: the plan's shape, into the next set
+    void upload_shape(Stage& st) {
+        if (!resident) return;
         const WitnessResident& r = *resident;
-        ud = r.in;
-        ud.o_aocl_path_off = r.o_aocl_path_off;
-        ud.o_entry_off = r.o_entry_off;
-        ud.o_path_off = r.o_path_off;
-        ud.o_rel_off = r.o_rel_off;
-        ud.o_aocl_path = r.out.o_aocl_path;
-        ud.o_chunk_index = r.out.o_chunk_index;
-        ud.o_path = r.out.o_path;
-        ud.o_rel = r.out.o_rel;
-        st.in(ud.wit_job, up.wit_job.data(), W);
-        st.in(d_in_ent_wit, up.in_ent_wit.data(), WE);
-        st.in(ud.o_key, up.chunk_index.data(), OE);  // the plan's keys; the store's are the device's (o_chunk_index)
-        st.in(ud.o_ent_wit, up.ent_wit.data(), OE);
-        st.in(ud.o_ent_src, up.ent_src.data(), OE);
-        st.tmp(d_wauth, WE);
-        st.tmp(ud.status, W, 2);
+        st.up(r.o_aocl_path_off, up.aocl_path_off.data(), W + 1);
+        st.up(r.o_entry_off, up.entry_off.data(), W + 1);
+        st.up(r.o_path_off, up.path_off.data(), OE + 1);
+        st.up(r.o_rel_off, up.rel_off.data(), OE + 1);
     }
-    // after commit(); a: the block's, its launches enqueued
-    void enqueue(Stage& st, nhip_ctx* c, const nhip::MsApplyDev& a) {
-        if (resident) {  // the plan's shape, into the next set
-            const WitnessResident& r = *resident;
-            st.up(r.o_aocl_path_off, up.aocl_path_off.data(), W + 1);
-            st.up(r.o_entry_off, up.entry_off.data(), W + 1);
-            st.up(r.o_path_off, up.path_off.data(), OE + 1);
-            st.up(r.o_rel_off, up.rel_off.data(), OE + 1);
-        }
-        ud.auth = d_wauth;
-        ud.err = ud.status + W;
-        const nhip::MsChunkAuthJobsDev auth{a.jobs, a.peaks, ud.ch, d_in_ent_wit, ud.wit_job, d_wauth};  // entry -> witness -> job
-        st.launch([&] { return nhip::launch_ms_chunk_auth_jobs(auth, WE, c->stream); });
-        st.launch([&] { return nhip::launch_ms_wit_admit(a, ud, W, c->stream); });
-        st.launch([&] { return nhip::launch_ms_wit_paths(a, ud, W, OE, c->stream); });
-        st.launch([&] { return nhip::launch_ms_wit_chunks(a, ud, OE, c->stream); });
-        st.launch([&] { return nhip::launch_ms_wit_seal(ud, W, c->stream); });
+    void store_seal(Stage& st, nhip_ctx* c) {
         if (resident)
             st.launch([&] { return nhip::launch_ms_store_seal(ud, resident->sticky, resident->sticky_next, W, c->stream); });
     }
@@ -272,14 +260,86 @@ struct WitnessPart {
     }
 };
 
-// One Stage over a block part and, for nhip_ms_update_batch and nhip_ms_store_update, the witness part behind it
-int run_parts(Stage& st, nhip_ctx* c, BlockPart& blk, WitnessPart* wit = nullptr) {
+// The witnesses' part of nhip_ms_update_batch (DESIGN.md §6g), behind a BlockPart that keeps its nodes: inputs that
+// passed ms_update_ok, the host plan, and an output that passed ms_updated_check for a fill.
+struct WitnessPart : WitnessIO {
+    const uint32_t* d_in_ent_wit = nullptr;  // per input entry: its witness
+    uint8_t* d_wauth = nullptr;
+
+    WitnessPart(const nhip_ms_update_in& wit, const nhip::MsUpdateCounts& wc, const nhip::MsUpdatePlan& plan,
+                nhip_ms_updated& out_, const WitnessResident* res = nullptr)
+        : WitnessIO(wit, wc, plan, out_, res) {}
+    void declare(Stage& st) {
+        declare_io(st, 2);  // per witness: status, error byte
+        st.in(d_in_ent_wit, up.in_ent_wit.data(), WE);
+        st.tmp(d_wauth, WE);
+    }
+    // after commit(); blk: the block's, its launches enqueued
+    void enqueue(Stage& st, nhip_ctx* c, const BlockPart& blk) {
+        const nhip::MsApplyDev& a = blk.a;
+        upload_shape(st);
+        ud.auth = d_wauth;
+        ud.err = ud.status + W;
+        const nhip::MsChunkAuthJobsDev auth{a.jobs, a.peaks, ud.ch, d_in_ent_wit, ud.wit_job, d_wauth};  // entry -> witness -> job
+        st.launch([&] { return nhip::launch_ms_chunk_auth_jobs(auth, WE, c->stream); });
+        st.launch([&] { return nhip::launch_ms_wit_admit(a, ud, W, c->stream); });
+        st.launch([&] { return nhip::launch_ms_wit_paths(a, ud, W, OE, c->stream); });
+        st.launch([&] { return nhip::launch_ms_wit_chunks(a, ud, OE, c->stream); });
+        st.launch([&] { return nhip::launch_ms_wit_seal(ud, W, c->stream); });
+        store_seal(st, c);
+    }
+};
+
+// The witnesses' part of nhip_ms_revert_batch, behind a BlockPart (whose kept nodes it does not
+// read: they are the values after the block): the witnesses as they stand after the block, ms_revert_plan's plan.
+// Every reverted witness is authenticated against msa_before where it was written: its AOCL part by
+// k_ms_rev_aocl_jobs (mmr_climb under the job's AOCL peaks, which are in the block's peak pool), its dictionary by
+// the block's own chunk authentication, before k_ms_rev_seal folds the results into the status.
+struct RevertPart : WitnessIO {
+    nhip::MsRevertDev rd{};
+    std::vector<uint64_t> node_off;
+    uint8_t *d_member = nullptr, *d_oauth = nullptr;
+
+    RevertPart(const nhip_ms_update_in& wit, const nhip::MsUpdateCounts& wc, const nhip::MsUpdatePlan& plan,
+               nhip_ms_updated& out_, const BlockPart& blk, const WitnessResident* res = nullptr)
+        : WitnessIO(wit, wc, plan, out_, res), node_off(nhip::ms_revert_node_offsets(blk.o.jobs)) {}
+    void declare(Stage& st) {
+        declare_io(st, 3);  // per witness: status, error byte, short-of byte
+        st.in(rd.node_off, node_off.data(), node_off.size());
+        st.tmp(rd.nodes, (size_t)node_off.back(), 5);
+        st.tmp(d_member, W);
+        st.tmp(d_oauth, OE);
+    }
+    void enqueue(Stage& st, nhip_ctx* c, const BlockPart& blk) {
+        const nhip::MsApplyDev& a = blk.a;
+        upload_shape(st);
+        ud.err = ud.status + W;
+        rd.short_of = ud.status + 2 * W;
+        rd.member = d_member;
+        rd.auth = d_oauth;
+        st.launch([&] { return nhip::launch_ms_revert_nodes(a, rd, blk.n, (size_t)blk.o.grp_total, c->stream); });
+        st.launch([&] { return nhip::launch_ms_rev_admit(a, ud, rd, W, c->stream); });
+        st.launch([&] { return nhip::launch_ms_rev_paths(a, ud, rd, W, OE, c->stream); });
+        st.launch([&] { return nhip::launch_ms_rev_chunks(a, ud, rd, OE, c->stream); });
+        // the verification: every reverted witness against its job's msa_before
+        st.launch([&] { return nhip::launch_ms_rev_aocl_jobs(a, ud, d_member, W, c->stream); });
+        const nhip::MsChunksDev after{ud.o_entry_off, ud.o_chunk_index, ud.o_path_off, ud.o_path, ud.o_rel_off, ud.o_rel};
+        const nhip::MsChunkAuthJobsDev auth{a.jobs, a.peaks, after, ud.o_ent_wit, ud.wit_job, d_oauth};  // entry -> witness -> job
+        st.launch([&] { return nhip::launch_ms_chunk_auth_jobs(auth, OE, c->stream); });
+        st.launch([&] { return nhip::launch_ms_rev_seal(ud, rd, W, c->stream); });
+        store_seal(st, c);
+    }
+};
+
+// One Stage over a block part and, for the update and revert calls, the witness part behind it
+template <class Wit = WitnessPart>
+int run_parts(Stage& st, nhip_ctx* c, BlockPart& blk, Wit* wit = nullptr) {
     blk.declare(st);
     if (wit) wit->declare(st);
     if (st.commit()) return st.finish();
     blk.enqueue(st, c);
     if (wit) {
-        wit->enqueue(st, c, blk.a);
+        wit->enqueue(st, c, blk);
         wit->read_back(st);
     }
     blk.read_back(st);
@@ -288,7 +348,8 @@ int run_parts(Stage& st, nhip_ctx* c, BlockPart& blk, WitnessPart* wit = nullptr
     if (wit) wit->write_outputs();
     return NHIP_OK;
 }
-int run_parts(nhip_ctx* c, BlockPart& blk, WitnessPart* wit = nullptr) {
+template <class Wit = WitnessPart>
+int run_parts(nhip_ctx* c, BlockPart& blk, Wit* wit = nullptr) {
     Stage st(c);
     return run_parts(st, c, blk, wit);
 }

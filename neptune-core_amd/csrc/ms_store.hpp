@@ -87,7 +87,8 @@ std::vector<uint64_t> ms_store_kept(const uint8_t* keep, size_t W);
 // the mirror of the selection alone (retain: the store's mirror afterwards)
 MsStoreMirror ms_store_selected_mirror(const MsStoreMirror& m, const MsStoreSelect& s);
 
-// ---- update: the plan's shape becomes the mirror's (offsets and keys), `status` (W bytes) its sticky bytes
+// ---- update and revert: the plan's shape (ms_update_plan's or ms_revert_plan's, one struct) becomes the mirror's
+// (offsets and keys), `status` (W bytes) its sticky bytes
 void ms_store_apply_plan(MsStoreMirror& m, MsUpdatePlan&& plan, const uint8_t* status);
 
 // ---- capacities: at least `need`, at least double `cap`; 0 when that passes `limit` elements

@@ -4,9 +4,11 @@
 //   shape : the four offset arrays and the sticky status bytes
 //   fixed : minimum, distances, aocl_leaf_index, aocl_leaf
 // each in two sets, current and next.  An update writes the next pools and shape and swaps them once the stream has
-// drained clean and the block ended NHIP_MS_OK; a retain gathers all three into the next sets and swaps all three.
+// drained clean and the block ended NHIP_MS_OK, and so does a revert (§6j), the same step in the other direction; a
+// retain gathers all three into the next sets and swaps all three.
 // The fixed set is double too because a gather cannot compact in place.  The host side is ms_store.cpp (the mirror
-// and every shape decision); the block and witness parts are ms_parts.hpp's, shared with nhip_ms_update_batch.
+// and every shape decision); the block and witness parts are ms_parts.hpp's, shared with nhip_ms_update_batch and
+// nhip_ms_revert_batch.
 #include "ms_parts.hpp"
 #include "ms_store.hpp"
 
@@ -125,6 +127,80 @@ void declare_select(Stage& st, const nhip_ms_store& s, const MsStoreSelect& sel,
     g.s_key = cur.key.p;
     g.s_path = cur.path.p;
     g.s_rel = cur.rel.p;
+}
+
+// One job across the store, the witness side bound to it: forward (§6g) or, with `back`, from the accumulator after
+// the block to msa_before (§6j).  The plan from the mirror, the witness kernels from the current set into the next,
+// k_ms_store_seal, the swap.
+int store_cross(nhip_ms_store* s, const nhip_ms_apply_in* block, nhip_ms_apply_out* block_out, uint8_t* status, bool back) {
+    nhip::MsApplyCounts cnt;
+    if (!s || !block || block->n_jobs != 1 || nhip::ms_apply_ok(block, block_out, &cnt)) return NHIP_ERR_ARG;
+    nhip_ctx* c = s->c;
+    try {
+        Stage st(c);
+        const size_t W = s->m.witnesses();
+        if (W == 0) {  // the block part alone
+            BlockPart blk(*block, *block_out, cnt, false);
+            return run_parts(st, c, blk);
+        }
+        uint64_t wit_off[2];
+        nhip_ms_chunks mirror_chunks;
+        nhip_ms_update_in win;
+        nhip::ms_store_as_update_in(s->m, wit_off, &mirror_chunks, &win);
+        const nhip::MsUpdateCounts wc = s->m.counts();
+        nhip::MsUpdatePlan plan;
+        int rc = back ? nhip::ms_revert_plan(block, &win, wc, &plan) : nhip::ms_update_plan(block, &win, wc, &plan);
+        if (rc != NHIP_OK) return rc;
+        const size_t OE = plan.chunk_index.size();
+        const uint64_t need[4] = {plan.aocl_path_off[W], OE, plan.path_off[OE], plan.rel_off[OE]}, none[4] = {0, 0, 0, 0};
+        Pools& cur = s->pools[s->pc];
+        Pools& nxt = s->pools[1 - s->pc];
+        Shape& hcur = s->shape[s->sc];
+        Shape& hnxt = s->shape[1 - s->sc];
+        const Fixed& F = s->fixed[s->fc];
+        if ((rc = nxt.ensure(need, none, c->stream)) != NHIP_OK) return rc;
+        if ((rc = hnxt.ensure(W, OE, 0, 0, false, c->stream)) != NHIP_OK) return rc;
+        WitnessResident res{};
+        res.in.minimum = F.minimum.p;
+        res.in.distances = F.distances.p;
+        res.in.aocl_leaf_index = F.leaf_index.p;
+        res.in.aocl_leaf = F.leaf.p;
+        res.in.aocl_path_off = hcur.aocl_path_off.p;
+        res.in.aocl_path = cur.aocl.p;
+        res.in.ch = s->chunks();
+        res.out.o_aocl_path = nxt.aocl.p;
+        res.out.o_chunk_index = nxt.key.p;
+        res.out.o_path = nxt.path.p;
+        res.out.o_rel = nxt.rel.p;
+        res.o_aocl_path_off = hnxt.aocl_path_off.p;
+        res.o_entry_off = hnxt.entry_off.p;
+        res.o_path_off = hnxt.path_off.p;
+        res.o_rel_off = hnxt.rel_off.p;
+        res.sticky = hcur.sticky.p;
+        res.sticky_next = hnxt.sticky.p;
+        nhip_ms_updated unused{};
+        BlockPart blk(*block, *block_out, cnt, !back);  // forward: k_ms_apply keeps its nodes
+        auto cross = [&](auto& part) -> int {
+            if (const int e = run_parts(st, c, blk, &part)) return e;
+            if (block_out->status[0] != NHIP_MS_OK) {  // the store stays as it was
+                if (status) std::fill(status, status + W, (uint8_t)NHIP_MS_JOB_REJECTED);
+                return NHIP_OK;
+            }
+            if (status) std::copy(part.wstatus.begin(), part.wstatus.end(), status);
+            s->pc = 1 - s->pc;
+            s->sc = 1 - s->sc;
+            nhip::ms_store_apply_plan(s->m, std::move(plan), part.wstatus.data());
+            return NHIP_OK;
+        };
+        if (back) {
+            RevertPart rp(win, wc, plan, unused, blk, &res);
+            return cross(rp);
+        }
+        WitnessPart wp(win, wc, plan, unused, &res);
+        return cross(wp);
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
 }
 
 }  // namespace
@@ -246,70 +322,12 @@ int nhip_ms_store_append(nhip_ms_store* s, const nhip_ms_update_in* wit, size_t 
     }
 }
 
-// §6g for one job, the witness side bound to the store: the plan from the mirror, the witness kernels from the
-// current set into the next, k_ms_store_seal, the swap.
 int nhip_ms_store_update(nhip_ms_store* s, const nhip_ms_apply_in* block, nhip_ms_apply_out* block_out, uint8_t* status) {
-    nhip::MsApplyCounts cnt;
-    if (!s || !block || block->n_jobs != 1 || nhip::ms_apply_ok(block, block_out, &cnt)) return NHIP_ERR_ARG;
-    nhip_ctx* c = s->c;
-    try {
-        Stage st(c);
-        const size_t W = s->m.witnesses();
-        if (W == 0) {  // the block part alone
-            BlockPart blk(*block, *block_out, cnt, false);
-            return run_parts(st, c, blk);
-        }
-        uint64_t wit_off[2];
-        nhip_ms_chunks mirror_chunks;
-        nhip_ms_update_in win;
-        nhip::ms_store_as_update_in(s->m, wit_off, &mirror_chunks, &win);
-        const nhip::MsUpdateCounts wc = s->m.counts();
-        nhip::MsUpdatePlan plan;
-        int rc = nhip::ms_update_plan(block, &win, wc, &plan);
-        if (rc != NHIP_OK) return rc;
-        const size_t OE = plan.chunk_index.size();
-        const uint64_t need[4] = {plan.aocl_path_off[W], OE, plan.path_off[OE], plan.rel_off[OE]}, none[4] = {0, 0, 0, 0};
-        Pools& cur = s->pools[s->pc];
-        Pools& nxt = s->pools[1 - s->pc];
-        Shape& hcur = s->shape[s->sc];
-        Shape& hnxt = s->shape[1 - s->sc];
-        const Fixed& F = s->fixed[s->fc];
-        if ((rc = nxt.ensure(need, none, c->stream)) != NHIP_OK) return rc;
-        if ((rc = hnxt.ensure(W, OE, 0, 0, false, c->stream)) != NHIP_OK) return rc;
-        WitnessResident res{};
-        res.in.minimum = F.minimum.p;
-        res.in.distances = F.distances.p;
-        res.in.aocl_leaf_index = F.leaf_index.p;
-        res.in.aocl_leaf = F.leaf.p;
-        res.in.aocl_path_off = hcur.aocl_path_off.p;
-        res.in.aocl_path = cur.aocl.p;
-        res.in.ch = s->chunks();
-        res.out.o_aocl_path = nxt.aocl.p;
-        res.out.o_chunk_index = nxt.key.p;
-        res.out.o_path = nxt.path.p;
-        res.out.o_rel = nxt.rel.p;
-        res.o_aocl_path_off = hnxt.aocl_path_off.p;
-        res.o_entry_off = hnxt.entry_off.p;
-        res.o_path_off = hnxt.path_off.p;
-        res.o_rel_off = hnxt.rel_off.p;
-        res.sticky = hcur.sticky.p;
-        res.sticky_next = hnxt.sticky.p;
-        nhip_ms_updated unused{};
-        BlockPart blk(*block, *block_out, cnt, true);  // k_ms_apply keeps its nodes
-        WitnessPart wp(win, wc, plan, unused, &res);
-        if ((rc = run_parts(st, c, blk, &wp)) != NHIP_OK) return rc;
-        if (block_out->status[0] != NHIP_MS_OK) {  // the store stays as it was
-            if (status) std::fill(status, status + W, (uint8_t)NHIP_MS_JOB_REJECTED);
-            return NHIP_OK;
-        }
-        if (status) std::copy(wp.wstatus.begin(), wp.wstatus.end(), status);
-        s->pc = 1 - s->pc;
-        s->sc = 1 - s->sc;
-        nhip::ms_store_apply_plan(s->m, std::move(plan), wp.wstatus.data());
-        return NHIP_OK;
-    } catch (const std::bad_alloc&) {
-        return NHIP_ERR_OOM;
-    }
+    return store_cross(s, block, block_out, status, false);
+}
+
+int nhip_ms_store_revert(nhip_ms_store* s, const nhip_ms_apply_in* block, nhip_ms_apply_out* block_out, uint8_t* status) {
+    return store_cross(s, block, block_out, status, true);
 }
 
 int nhip_ms_store_read(nhip_ms_store* s, const uint64_t* sel_in, size_t n_sel, nhip_ms_updated* out) {

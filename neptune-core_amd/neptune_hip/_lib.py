@@ -305,6 +305,10 @@ SIGNATURES = {
                             ctypes.c_int),
     "nhip_ms_update_batch": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut), ctypes.POINTER(MsUpdateIn),
                               ctypes.POINTER(MsUpdated)], ctypes.c_int),
+    "nhip_ms_revert_plan": ([ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsUpdateIn), ctypes.POINTER(MsUpdated)],
+                            ctypes.c_int),
+    "nhip_ms_revert_batch": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut), ctypes.POINTER(MsUpdateIn),
+                              ctypes.POINTER(MsUpdated)], ctypes.c_int),
     "nhip_proof_decodes": ([_vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof)],
                            ctypes.c_int),
     "nhip_verify_batch": ([_vp, _vp, ctypes.POINTER(StarkParams), ctypes.POINTER(Claim), ctypes.POINTER(Proof),
@@ -368,6 +372,7 @@ SIGNATURES = {
     "nhip_ms_store_count": ([_vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "nhip_ms_store_append": ([_vp, ctypes.POINTER(MsUpdateIn), _sz], ctypes.c_int),
     "nhip_ms_store_update": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut), _vp], ctypes.c_int),
+    "nhip_ms_store_revert": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut), _vp], ctypes.c_int),
     "nhip_ms_store_read": ([_vp, _vp, _sz, ctypes.POINTER(MsUpdated)], ctypes.c_int),
     "nhip_ms_store_retain": ([_vp, _vp], ctypes.c_int),
     "nhip_ms_store_check": ([_vp, ctypes.POINTER(Msa), _vp, _vp, _vp, _vp], ctypes.c_int),

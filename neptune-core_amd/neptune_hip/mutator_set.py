@@ -25,6 +25,12 @@ consensus step after "the proof verifies", batched.
   host half (the shapes, no GPU), `update_membership_proofs` and `update_removal_records` are the wallet's and the
   mempool's calls (state/wallet/wallet_state.rs:1375,1481; state/mod.rs:1537,1557,2507,2522).
 
+* `revert_witnesses_batch(ctx, jobs)` — `MsMembershipProof::revert_update_from_remove` /
+  `revert_update_from_batch_addition` (ms_membership_proof.rs:380-413,517-557) over whole blocks, as the end state
+  (DESIGN.md §6j): witnesses standing after a block taken back to the accumulator before it, each verified there;
+  `revert_plan_batch(jobs)` is its host half, `revert_membership_proofs` the wallet's call during a reorganisation
+  (state/mod.rs:1392-1497), and `WitnessStore.revert` the same for witnesses resident on the device.
+
 The types mirror the reference's over numpy; every verdict is the device's.  Where the reference
 would panic or truncate (an index past the active window, or >= 2^76) the record is rejected with
 `OUT_OF_RANGE`.
@@ -418,10 +424,13 @@ class Witness:
 class PackedUpdate:
     """The arguments of `nhip_ms_update_plan` / `nhip_ms_update_batch` over numpy arrays.  `jobs`: `(msa_before,
     MutatorSetUpdate, witnesses)` triples.  `apply` is the block half (`PackedApply`), `win` the witnesses' struct,
-    `out` the output arrays once `plan` or `run` has sized them."""
+    `out` the output arrays once `plan` or `run` has sized them.  `revert`: the same structs for
+    `nhip_ms_revert_plan` / `nhip_ms_revert_batch`, the witnesses standing after the block."""
 
-    def __init__(self, jobs, expected=None):
+    def __init__(self, jobs, expected=None, revert=False):
         self.n = len(jobs)
+        self.plan_name, self.batch_name = (("nhip_ms_revert_plan", "nhip_ms_revert_batch") if revert else
+                                           ("nhip_ms_update_plan", "nhip_ms_update_batch"))
         self.apply = PackedApply([(m, u) for m, u, _ in jobs], expected)
         wits = self.witnesses = [w for _, _, ws in jobs for w in ws]
         W = self.n_witnesses = len(wits)
@@ -444,16 +453,16 @@ class PackedUpdate:
 
     def _call(self, lib, handle):
         if handle is None:
-            return lib.nhip_ms_update_plan(ctypes.byref(self.apply.cin), ctypes.byref(self.win), ctypes.byref(self.cout))
-        return lib.nhip_ms_update_batch(handle, ctypes.byref(self.apply.cin), ctypes.byref(self.apply.cout),
-                                        ctypes.byref(self.win), ctypes.byref(self.cout))
+            return getattr(lib, self.plan_name)(ctypes.byref(self.apply.cin), ctypes.byref(self.win), ctypes.byref(self.cout))
+        return getattr(lib, self.batch_name)(handle, ctypes.byref(self.apply.cin), ctypes.byref(self.apply.cout),
+                                             ctypes.byref(self.win), ctypes.byref(self.cout))
 
     def run(self, lib, handle=None) -> int:
         """Both calls of the two-call pattern; with no `handle` the host plan alone (statuses, digests and chunk
         words stay zero).  Returns the second call's code; `out` holds the arrays."""
         W = self.n_witnesses
         self.cout = _lib.MsUpdated()
-        rc = lib.nhip_ms_update_plan(ctypes.byref(self.apply.cin), ctypes.byref(self.win), ctypes.byref(self.cout))
+        rc = getattr(lib, self.plan_name)(ctypes.byref(self.apply.cin), ctypes.byref(self.win), ctypes.byref(self.cout))
         if rc != _lib.NHIP_OK:
             return rc
         A, E, PD, RW = (int(getattr(self.cout, f)) for f in ("aocl_digests", "entries", "path_digests", "rel_words"))
@@ -484,10 +493,14 @@ def update_witnesses_batch(ctx, jobs, expected=None):
     job `(verdict, status, bad_record, msa_after, witnesses)` with the first four as `apply_update_batch` gives them
     and `witnesses` a list of `(status, Witness after the block or None)`: a witness is brought up to date only when
     its job's status is OK and it passes admission against `msa_before` (the order of `nhip_ms_update_batch`)."""
+    return _witnesses_batch(ctx, jobs, expected, False)
+
+
+def _witnesses_batch(ctx, jobs, expected, revert):
     if len(jobs) == 0:
         return []
-    pu = PackedUpdate(jobs, expected)
-    check(pu.run(ctx.lib, ctx.handle), "nhip_ms_update_batch")
+    pu = PackedUpdate(jobs, expected, revert)
+    check(pu.run(ctx.lib, ctx.handle), pu.batch_name)
     block = _apply_results(pu.apply)
     o = pu.out
     dictionaries = unpack_chunks(pu.dictionaries())
@@ -511,6 +524,10 @@ def update_membership_proofs(ctx, msa_before: MutatorSetAccumulator, update: Mut
     up to the accumulator after `update`.  The index sets (`AbsoluteIndexSet::compute`) and the AOCL leaves
     (`hash_pair(hash_pair(item, sender_randomness), hash_pair(receiver_preimage, 0))`) are derived on the device.
     `(job status, msa_after or None, [(status, MsMembershipProof or None)])`."""
+    return _membership_proofs(ctx, msa_before, update, items, proofs, False)
+
+
+def _membership_proofs(ctx, msa_before, update, items, proofs, revert):
     if len(items) != len(proofs):
         raise ValueError("one membership proof per item")
     wits = []
@@ -522,7 +539,7 @@ def update_membership_proofs(ctx, msa_before: MutatorSetAccumulator, update: Mut
         leaves = ctx.hash_pair(ctx.hash_pair(it, sr), ctx.hash_pair(rp, np.zeros_like(rp)))
         wits = [Witness(s, list(p.target_chunks), int(p.aocl_leaf_index), [int(x) for x in leaf], list(p.auth_path_aocl))
                 for s, p, leaf in zip(sets, proofs, leaves)]
-    _, status, _, after, ws = update_witnesses_batch(ctx, [(msa_before, update, wits)])[0]
+    _, status, _, after, ws = _witnesses_batch(ctx, [(msa_before, update, wits)], None, revert)[0]
     out = [(st, None if w is None else MsMembershipProof(p.sender_randomness, p.receiver_preimage, w.auth_path_aocl,
                                                          p.aocl_leaf_index, w.target_chunks))
            for (st, w), p in zip(ws, proofs)]
@@ -537,6 +554,33 @@ def update_removal_records(ctx, msa_before: MutatorSetAccumulator, update: Mutat
     wits = [Witness(r.absolute_indices, list(r.target_chunks)) for r in records]
     _, status, _, after, ws = update_witnesses_batch(ctx, [(msa_before, update, wits)])[0]
     return status, after, [(st, None if w is None else RemovalRecord(w.absolute_indices, w.target_chunks)) for st, w in ws]
+
+
+# ---------------------------------------------------------------- witnesses back across a block
+def revert_plan_batch(jobs):
+    """The host half of `revert_witnesses_batch` (no GPU): the output arrays as `nhip_ms_revert_plan` lays them out
+    (`aocl_path_off`, `entry_off`, `chunk_index`, `path_off`, `rel_off`; the rest zero)."""
+    pu = PackedUpdate(jobs, revert=True)
+    check(pu.run(_lib.load()), "nhip_ms_revert_plan")
+    return pu.out
+
+
+def revert_witnesses_batch(ctx, jobs, expected=None):
+    """`jobs`: `(MutatorSetAccumulator before, MutatorSetUpdate, [Witness])` triples as `update_witnesses_batch` takes
+    them, but the witnesses stand at the accumulator *after* the block and are taken back to `msa_before`
+    (`expected`: that accumulator after, checked by rule 2.e).  Per job `(verdict, status, bad_record, msa_after,
+    witnesses)`, `witnesses` a list of `(status, Witness before the block or None)`: a witness comes back only when
+    its job's status is OK, it passes admission and, reverted, it authenticates against `msa_before` (the order of
+    `nhip_ms_revert_batch`)."""
+    return _witnesses_batch(ctx, jobs, expected, True)
+
+
+def revert_membership_proofs(ctx, msa_before: MutatorSetAccumulator, update: MutatorSetUpdate, items,
+                             proofs: Sequence[MsMembershipProof]):
+    """The wallet's step for an abandoned block during a reorganisation (state/mod.rs:1392-1497): every monitored
+    UTXO's membership proof, standing after `update`, taken back to `msa_before`.  A proof born in the block gets
+    NOT_IN_AOCL.  `(job status, msa_after or None, [(status, MsMembershipProof or None)])`."""
+    return _membership_proofs(ctx, msa_before, update, items, proofs, True)
 
 
 # ---------------------------------------------------------------- witnesses resident on the device (DESIGN.md §6i)
@@ -565,7 +609,8 @@ class PackedWitnesses:
 class WitnessStore:
     """Membership proofs and removal records kept on the device across blocks (`nhip_ms_store_*`): `append` uploads
     witnesses once, `update` brings all of them across one block where they lie (only the block goes up and one
-    status byte per witness comes back), `read` copies chosen ones out, `retain` drops the others, `check` answers
+    status byte per witness comes back), `revert` takes all of them back across one when the tip moves to another
+    fork, `read` copies chosen ones out, `retain` drops the others, `check` answers
     "which of them verify / can still be removed" against an accumulator.  Witnesses keep their positions
     `0 .. len - 1` in insertion order until `retain`.  A witness whose status after an update is not OK keeps that
     status (and zeroed slots) until `retain` drops it.  `initial`: a dict of initial capacities (`witnesses`,
@@ -608,10 +653,18 @@ class WitnessStore:
     def update(self, msa_before, update, expected=None):
         """One block: `((verdict, status, bad_record, msa_after), [status of every witness])`.  Unless the block's
         status is OK the store is unchanged and every witness status is JOB_REJECTED."""
+        return self._cross("nhip_ms_store_update", msa_before, update, expected)
+
+    def revert(self, msa_before, update, expected=None):
+        """One block back: the store stands at the accumulator after `update` (`expected`, when given, is checked to
+        be that accumulator) and is taken to `msa_before`.  Returns what `update` returns, under the same contract;
+        a witness born in the block, or one that does not authenticate against `msa_before`, fails and stays failed."""
+        return self._cross("nhip_ms_store_revert", msa_before, update, expected)
+
+    def _cross(self, name, msa_before, update, expected):
         pa = PackedApply([(msa_before, update)], None if expected is None else [expected])
         status = np.zeros(max(len(self), 1), dtype=np.uint8)
-        check(self.ctx.lib.nhip_ms_store_update(self._h, ctypes.byref(pa.cin), ctypes.byref(pa.cout), status.ctypes.data),
-              "nhip_ms_store_update")
+        check(getattr(self.ctx.lib, name)(self._h, ctypes.byref(pa.cin), ctypes.byref(pa.cout), status.ctypes.data), name)
         return _apply_results(pa)[0], [int(x) for x in status[:len(self)]]
 
     def read_raw(self, indices=None):

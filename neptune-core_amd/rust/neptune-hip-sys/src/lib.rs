@@ -673,6 +673,10 @@ extern "C" {
                                out: *mut nhip_ms_updated) -> c_int;
     pub fn nhip_ms_update_batch(ctx: *mut nhip_ctx, block: *const nhip_ms_apply_in, block_out: *mut nhip_ms_apply_out,
                                 wit: *const nhip_ms_update_in, out: *mut nhip_ms_updated) -> c_int;
+    pub fn nhip_ms_revert_plan(block: *const nhip_ms_apply_in, wit: *const nhip_ms_update_in,
+                               out: *mut nhip_ms_updated) -> c_int;
+    pub fn nhip_ms_revert_batch(ctx: *mut nhip_ctx, block: *const nhip_ms_apply_in, block_out: *mut nhip_ms_apply_out,
+                                wit: *const nhip_ms_update_in, out: *mut nhip_ms_updated) -> c_int;
     pub fn nhip_ms_store_create(ctx: *mut nhip_ctx, initial: *const nhip_ms_store_caps,
                                 out: *mut *mut nhip_ms_store) -> c_int;
     pub fn nhip_ms_store_destroy(store: *mut nhip_ms_store);
@@ -680,6 +684,8 @@ extern "C" {
                                entries: *mut u64, path_digests: *mut u64, rel_words: *mut u64) -> c_int;
     pub fn nhip_ms_store_append(store: *mut nhip_ms_store, wit: *const nhip_ms_update_in, n: usize) -> c_int;
     pub fn nhip_ms_store_update(store: *mut nhip_ms_store, block: *const nhip_ms_apply_in,
+                                block_out: *mut nhip_ms_apply_out, status: *mut u8) -> c_int;
+    pub fn nhip_ms_store_revert(store: *mut nhip_ms_store, block: *const nhip_ms_apply_in,
                                 block_out: *mut nhip_ms_apply_out, status: *mut u8) -> c_int;
     pub fn nhip_ms_store_read(store: *mut nhip_ms_store, sel: *const u64, n_sel: usize,
                               out: *mut nhip_ms_updated) -> c_int;
