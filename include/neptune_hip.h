@@ -1001,6 +1001,92 @@ int nhip_ms_store_retain(nhip_ms_store *store, const uint8_t *keep);
 int nhip_ms_store_check(nhip_ms_store *store, const nhip_msa *msa, uint8_t *aocl_member, uint8_t *valid,
                         uint8_t *can_remove, uint8_t *status);
 
+/* ---- the archival mutator set resident on the device ----------------------------
+ * ArchivalMutatorSet (util_types/mutator_set/archival_mutator_set.rs over util_types/archival_mmr.rs): every node of
+ * the AOCL MMR and of the inactive-SWBF MMR, every chunk and the active window, in device memory of the archive's
+ * own: the structure fresh witnesses come from.  An MMR of n leaves is kept as level arrays: level h holds the n >> h
+ * nodes (h, k), each the root of the leaves [k 2^h, (k + 1) 2^h); the authentication path of leaf i is the nodes
+ * (t, (i >> t) ^ 1) for t < ilog2(i ^ n), leaf sibling first, the shape nhip_mmr_verify_batch reads.  The chunks'
+ * words (sorted ascending, repeats kept: Chunk::insert, chunk.rs:55-64) lie in a u32 arena behind an
+ * (offset, length) table.  The host keeps a mirror of the integers alone (both leaf counts, the chunk table, the
+ * window, the capacities) and no digest.  An archive belongs to one nhip_ctx (which must outlive it) and to one tip;
+ * calls on it are serialized by the context.
+ *   - NHIP_ERR_ARG, NHIP_ERR_OOM and NHIP_ERR_HIP before the first launch that writes archive state leave the archive
+ *     unchanged; a HIP error behind such a launch poisons it: every later call returns NHIP_ERR_HIP, so that nothing
+ *     is ever read from a half-written archive.
+ *   - Digests are computed on the device only: load accepts leaves, chunk words and the window, nothing precomputed.
+ * Load builds level h with a launch of its own while level h - 1 has more than NHIP_MS_ARCHIVE_TAIL_NODES nodes, and
+ * all levels above with one workgroup per MMR. */
+#define NHIP_MS_ARCHIVE_TAIL_NODES 256
+typedef struct nhip_ms_archive nhip_ms_archive;
+/* initial capacities (0: none): AOCL leaves, chunks, chunk words; every capacity grows geometrically on demand, device
+ * to device */
+typedef struct {
+    size_t aocl_leafs, chunks, rel_words;
+} nhip_ms_archive_caps;
+int nhip_ms_archive_create(nhip_ctx *ctx, const nhip_ms_archive_caps *initial, nhip_ms_archive **out);
+void nhip_ms_archive_destroy(nhip_ms_archive *archive);
+/* the totals, from the host mirror; any pointer may be NULL.  rel_live: the chunk words the chunks own; rel_dead:
+ * arena words no chunk owns any more. */
+int nhip_ms_archive_count(const nhip_ms_archive *archive, uint64_t *aocl_leafs, uint64_t *chunks, uint64_t *n_active,
+                          uint64_t *rel_live, uint64_t *rel_dead);
+/* Bulk load into an empty archive: n_leafs AOCL leaves (addition records' canonical commitments, 5 words each), the
+ * n_chunks chunks' words rel[rel_off[c] .. rel_off[c + 1]) and the window.  Uploads them once, hashes every chunk
+ * (Tip5::hash(chunk)) and builds every level of both MMRs on the device.  NHIP_ERR_ARG before anything is touched: an
+ * archive that is not empty, an unsorted chunk or window, offsets that do not start at 0 or that decrease, a relative
+ * index >= 4096 in a chunk or >= 2^20 in the window, n_chunks != batch_index(n_leafs) (util_types/mutator_set.rs:74-76). */
+int nhip_ms_archive_load(nhip_ms_archive *archive, const uint64_t *aocl_leaves, uint64_t n_leafs,
+                         const uint64_t *rel_off, const uint32_t *rel, uint64_t n_chunks, const uint32_t *active,
+                         uint64_t n_active);
+/* The archive's MutatorSetAccumulator as one job's worth of nhip_ms_apply_out: both peak lists (read from the level
+ * arrays on the device), the counts and the window (capacity active_off[1] - active_off[0] >= n_active, else
+ * NHIP_ERR_ARG); verdict 1, status NHIP_MS_OK and bad_record UINT64_MAX where those pointers are present. */
+int nhip_ms_archive_accumulator(nhip_ms_archive *archive, nhip_ms_apply_out *out);
+/* ArchivalState::update_mutator_set's forward step (state/archival_state.rs:1242-1409) as an end state; block->n_jobs
+ * == 1 and the accumulator outputs of block_out present (else NHIP_ERR_ARG).  The block runs through steps 1-5 of
+ * nhip_ms_apply_batch with block->msa_before[0] checked against the archive's own accumulator first: both counts, the
+ * window's length and words (against the mirror) and both peak lists (against the level arrays); any difference is
+ * NHIP_MS_INCONSISTENT (verdict 0, bad_record UINT64_MAX, zero counts).  Unless the job ends NHIP_MS_OK the archive is
+ * unchanged in every count and byte a later call can observe, and block_out is as nhip_ms_apply_batch fills it.  On
+ * NHIP_MS_OK the AOCL gains the additions' commitments; every chunk c with b0 <= c < b1 is created from the part
+ * [4096 (c - b0), 4096 (c - b0 + 1)) of the old window made relative (empty from c - b0 = 256 on); every chunk below b1
+ * that the records' indices hit is merged with those indices, repeats kept; the SWBF MMR gets the new and the changed
+ * leaves with all their ancestors; the window becomes the accumulator-after's.  A chunk that changes is written anew
+ * at the arena's tail and its old words are dead; when dead words exceed live words after an apply the arena is
+ * compacted into a second buffer with one gather and the two are swapped.  Every array grows geometrically, device to
+ * device; all allocation and growth precede the first launch that writes archive state, and the mirror and the counts
+ * advance only after the stream drains clean.  Afterwards nhip_ms_archive_accumulator equals what block_out reported. */
+int nhip_ms_archive_apply(nhip_ms_archive *archive, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out);
+/* ArchivalMmr::prove_membership_async (archival_mmr.rs:297-321) for n leaves of one MMR (which: 0 AOCL, 1 SWBF):
+ * path_off n + 1, in digests.  Two-call sizing: with path_off and path NULL only *path_digests is written (from the
+ * mirror alone); otherwise path_cap >= the total, else NHIP_ERR_ARG.  An index >= the leaf count is NHIP_ERR_ARG with
+ * the outputs untouched.  One gather on the device, then one copy. */
+int nhip_ms_archive_paths(nhip_ms_archive *archive, int which, const uint64_t *leaf_index, size_t n,
+                          uint64_t *path_off, uint64_t *path, size_t path_cap, size_t *path_digests);
+/* ArchivalMmr::get_leaf_range_inclusive_async (archival_mmr.rs:211-229): the leaves first .. first + n - 1 of one MMR;
+ * a range that leaves the MMR is NHIP_ERR_ARG with `out` untouched. */
+int nhip_ms_archive_leaves(nhip_ms_archive *archive, int which, uint64_t first, uint64_t n, uint64_t *out);
+/* Fresh witnesses for n index sets (the layout nhip_absolute_index_sets writes), in the layout of nhip_ms_updated,
+ * which nhip_ms_store_append reads.  With an AOCL leaf index it is ArchivalMutatorSet::restore_membership_proof
+ * (archival_mutator_set.rs:298-346); with aocl_leaf_index == UINT64_MAX the dictionary alone, as
+ * restore_membership_proof_privacy_preserving (:350-406) and the refresh of old removal records
+ * (state/archival_state.rs:1156-1179) need it.  Per witness the status is the first failure of
+ *   NHIP_MS_NOT_IN_AOCL   the leaf index is >= the leaf count, or the archive is empty (the reference's
+ *                         RequestedAoclAuthPathOutOfBounds / MutatorSetIsEmpty);
+ *   NHIP_MS_OUT_OF_RANGE  minimum + distance saturates u128, or a chunk index exceeds batch_index + 255;
+ * such a witness owns no digest and no entry.  Otherwise: the AOCL path of ilog2(l ^ n) digests; a dictionary whose
+ * keys are the witness's distinct chunk indices below the batch index b, strictly ascending (chunk_dictionary.rs:29-45),
+ * each with the chunk's words and its path of ilog2(key ^ b) digests.  Every length and every status is an integer
+ * decision of the plan; two-call sizing as nhip_ms_store_read (the count pass reads the mirror alone). */
+int nhip_ms_archive_restore(nhip_ms_archive *archive, const uint64_t *minimum, const uint32_t *distances,
+                            const uint64_t *aocl_leaf_index, size_t n, nhip_ms_updated *out);
+/* The shape and every status of nhip_ms_archive_restore from integers alone (no context, host only): an archive of
+ * aocl_leafs leaves whose chunk c holds chunk_len[c] words, n_chunks == batch_index(aocl_leafs) (else NHIP_ERR_ARG).
+ * Writes the offset arrays, the keys, the totals and, when present, status; aocl_path, path and rel are left alone. */
+int nhip_ms_archive_restore_plan(uint64_t aocl_leafs, const uint64_t *chunk_len, uint64_t n_chunks,
+                                 const uint64_t *minimum, const uint32_t *distances, const uint64_t *aocl_leaf_index,
+                                 size_t n, nhip_ms_updated *out);
+
 /* ---- a block file's mutator-set and transaction rules ---------------------------
  * Block::validate rules 2.a-2.l (protocol/consensus/block/mod.rs:811-891) for every (parent, child) pair of
  * scanned blocks, from the file's bytes: msa_before is the parent's Block::mutator_set_accumulator_after

@@ -193,6 +193,14 @@ class MsStoreCaps(ctypes.Structure):
 MS_STORE_GATHER_UNIT = 1024  # NHIP_MS_STORE_GATHER_UNIT: 8-byte destination words per work unit of the gather
 
 
+class MsArchiveCaps(ctypes.Structure):
+    """nhip_ms_archive_caps: the initial capacities of an archival mutator set (0: a default)."""
+    _fields_ = [("aocl_leafs", ctypes.c_size_t), ("chunks", ctypes.c_size_t), ("rel_words", ctypes.c_size_t)]
+
+
+MS_ARCHIVE_TAIL_NODES = 256  # NHIP_MS_ARCHIVE_TAIL_NODES: load gives a level a launch of its own while the level below has more nodes
+
+
 class BlkMsParams(ctypes.Structure):
     """nhip_blk_ms_params: the type-script digests, the pow tree height and the limits of rules 2.j-2.l."""
     _fields_ = [("native_currency_hash", ctypes.c_uint64 * 5), ("time_lock_hash", ctypes.c_uint64 * 5),
@@ -376,6 +384,17 @@ SIGNATURES = {
     "nhip_ms_store_read": ([_vp, _vp, _sz, ctypes.POINTER(MsUpdated)], ctypes.c_int),
     "nhip_ms_store_retain": ([_vp, _vp], ctypes.c_int),
     "nhip_ms_store_check": ([_vp, ctypes.POINTER(Msa), _vp, _vp, _vp, _vp], ctypes.c_int),
+    "nhip_ms_archive_create": ([_vp, ctypes.POINTER(MsArchiveCaps), ctypes.POINTER(_vp)], ctypes.c_int),
+    "nhip_ms_archive_destroy": ([_vp], None),
+    "nhip_ms_archive_count": ([_vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "nhip_ms_archive_load": ([_vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64], ctypes.c_int),
+    "nhip_ms_archive_accumulator": ([_vp, ctypes.POINTER(MsApplyOut)], ctypes.c_int),
+    "nhip_ms_archive_apply": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut)], ctypes.c_int),
+    "nhip_ms_archive_paths": ([_vp, ctypes.c_int, _vp, _sz, _vp, _vp, _sz, ctypes.POINTER(_sz)], ctypes.c_int),
+    "nhip_ms_archive_leaves": ([_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp], ctypes.c_int),
+    "nhip_ms_archive_restore": ([_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(MsUpdated)], ctypes.c_int),
+    "nhip_ms_archive_restore_plan": ([ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp, _vp, _sz,
+                                      ctypes.POINTER(MsUpdated)], ctypes.c_int),
     "nhip_blk_ms_params_default": ([ctypes.POINTER(BlkMsParams)], None),
     "nhip_blk_ms_walk": ([_vp, _sz, ctypes.c_uint32, _vp, _sz, ctypes.POINTER(BlkMsParts)], ctypes.c_int),
     "nhip_blk_guesser_fee_records": ([_vp, _vp, _sz, ctypes.POINTER(BlkMsParams), _vp, _sz, _vp, _vp, _vp, _vp],

@@ -722,3 +722,218 @@ class WitnessStore:
         check(self.ctx.lib.nhip_ms_store_check(self._h, ctypes.byref(cm), *(x.ctypes.data for x in a)),
               "nhip_ms_store_check")
         return [(bool(a[0][i]), bool(a[1][i]), bool(a[2][i]), int(a[3][i])) for i in range(n)]
+
+
+# ---------------------------------------------------------------- the archival mutator set on the device
+WINDOW_SIZE = 1 << 20
+
+
+def aocl_range(index_set: AbsoluteIndexSet) -> Tuple[int, int]:
+    """`AbsoluteIndexSet::aocl_range` (absolute_index_set.rs:174-220): the inclusive range of AOCL leaf indices an
+    item with this index set can have, whatever the AOCL's length.  An index is a relative index below WINDOW_SIZE
+    plus `batch_index * CHUNK_SIZE`, and a batch holds BATCH_SIZE leaves: the lowest batch is the first whose window
+    reaches the largest index, the highest the last whose window begins at or before the smallest.  ValueError where
+    the reference gives AbsoluteIndexExceedsTheoreticalBound."""
+    mn, spread = int(index_set.minimum), max(int(d) for d in index_set.distances)
+    if spread >= WINDOW_SIZE:
+        raise ValueError("AbsoluteIndexExceedsTheoreticalBound")
+    lo_batch = -(-max(mn + spread - (WINDOW_SIZE - 1), 0) // CHUNK_SIZE)
+    hi_batch = mn // CHUNK_SIZE
+    lo, hi = lo_batch * BATCH_SIZE, hi_batch * BATCH_SIZE + BATCH_SIZE - 1
+    if lo_batch >= 1 << 64 or hi_batch >= 1 << 64 or lo >= 1 << 64 or hi >= 1 << 64:
+        raise ValueError("AbsoluteIndexExceedsTheoreticalBound")
+    return lo, hi
+
+
+class Archive:
+    """`ArchivalMutatorSet` (util_types/mutator_set/archival_mutator_set.rs) resident on the device
+    (`nhip_ms_archive_*`): every node of both MMRs, every chunk and the window.  `load` uploads a whole set once and
+    builds every digest on the device; `apply` advances it across one block; `accumulator` reads the `MutatorSetAccumulator`; `aocl_paths`, `swbf_paths`
+    and `leaves` are the archival MMRs' `prove_membership` and `get_leaf_range_inclusive`;
+    `restore_membership_proofs`, `restore_dictionaries` and `restore_privacy_preserving` make fresh witnesses, in
+    the form `WitnessStore.append` takes.  `initial`: a dict of initial capacities (`aocl_leafs`, `chunks`,
+    `rel_words`), or None."""
+
+    def __init__(self, ctx, initial=None):
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        caps = _lib.MsArchiveCaps(**initial) if initial else None
+        check(ctx.lib.nhip_ms_archive_create(ctx.handle, ctypes.byref(caps) if caps else None, ctypes.byref(self._h)),
+              "nhip_ms_archive_create")
+
+    def close(self):
+        if self._h:
+            self.ctx.lib.nhip_ms_archive_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def counts(self):
+        """`(aocl_leafs, chunks, n_active, rel_live, rel_dead)` from the host mirror."""
+        c = (ctypes.c_uint64 * 5)()
+        check(self.ctx.lib.nhip_ms_archive_count(self._h, *(ctypes.addressof(c) + 8 * i for i in range(5))),
+              "nhip_ms_archive_count")
+        return tuple(int(x) for x in c)
+
+    def load_raw(self, leaves, rel_off, rel, active) -> int:
+        """`nhip_ms_archive_load` over arrays as given; the return code."""
+        leaves = np.ascontiguousarray(np.asarray(leaves, dtype=np.uint64)).reshape(-1, 5)
+        rel_off = np.ascontiguousarray(np.asarray(rel_off, dtype=np.uint64)).reshape(-1)
+        rel = np.ascontiguousarray(np.asarray(rel, dtype=np.uint32)).reshape(-1)
+        active = np.ascontiguousarray(np.asarray(active, dtype=np.uint32)).reshape(-1)
+        return self.ctx.lib.nhip_ms_archive_load(self._h, _ptr(leaves), leaves.shape[0], _ptr(rel_off), _ptr(rel),
+                                                 max(rel_off.size, 1) - 1, _ptr(active), active.size)
+
+    def load(self, aocl_leaves, chunks, active=()):
+        """Into an empty archive: the AOCL leaves (addition records' canonical commitments), chunk c's relative
+        indices `chunks[c]` (sorted) for every c below the batch index, and the window (sorted)."""
+        rel_off = _csr([len(ch) for ch in chunks])
+        rel = [int(x) for ch in chunks for x in ch]
+        leaves = _digests(aocl_leaves) if len(aocl_leaves) else np.zeros((0, 5), dtype=np.uint64)
+        check(self.load_raw(leaves, rel_off, rel, list(active)), "nhip_ms_archive_load")
+
+    def apply(self, msa_before, update, expected=None):
+        """One block (`ArchivalState::update_mutator_set`'s forward step): `(verdict, status, bad_record, msa_after)`
+        as `apply_update_batch` gives them.  `msa_before` has to be the archive's own accumulator (else INCONSISTENT);
+        unless the status is OK the archive is unchanged."""
+        pa = PackedApply([(msa_before, update)], None if expected is None else [expected])
+        check(self.ctx.lib.nhip_ms_archive_apply(self._h, ctypes.byref(pa.cin), ctypes.byref(pa.cout)),
+              "nhip_ms_archive_apply")
+        return _apply_results(pa)[0]
+
+    def accumulator(self) -> MutatorSetAccumulator:
+        n_active = self.counts()[2]
+        z = lambda dtype, *shape: np.zeros(shape, dtype=dtype)  # noqa: E731
+        a = dict(verdict=z(np.uint8, 1), status=z(np.uint8, 1), bad_record=z(np.uint64, 1),
+                 aocl_peaks=z(np.uint64, 1, 64, 5), aocl_n_peaks=z(np.uint32, 1), aocl_num_leafs=z(np.uint64, 1),
+                 swbf_peaks=z(np.uint64, 1, 64, 5), swbf_n_peaks=z(np.uint32, 1), swbf_num_leafs=z(np.uint64, 1),
+                 active_off=np.asarray([0, n_active], dtype=np.uint64), active=z(np.uint32, max(n_active, 1)),
+                 n_active=z(np.uint64, 1))
+        cout = _lib.MsApplyOut(*(a[f].ctypes.data for f, _ in _lib.MsApplyOut._fields_))
+        check(self.ctx.lib.nhip_ms_archive_accumulator(self._h, ctypes.byref(cout)), "nhip_ms_archive_accumulator")
+        mmrs = [MmrAccumulator([tuple(int(x) for x in d) for d in a[w + "_peaks"][0, :int(a[w + "_n_peaks"][0])]],
+                               int(a[w + "_num_leafs"][0])) for w in ("aocl", "swbf")]
+        return MutatorSetAccumulator(mmrs[0], mmrs[1], [int(x) for x in a["active"][:int(a["n_active"][0])]])
+
+    def paths_raw(self, which: int, leaf_indices):
+        """Both calls of the two-call pattern: `(path_off, path)`."""
+        idx = np.ascontiguousarray(np.asarray(list(leaf_indices), dtype=np.uint64))
+        n = idx.size
+        total = ctypes.c_size_t()
+        check(self.ctx.lib.nhip_ms_archive_paths(self._h, which, _ptr(idx), n, None, None, 0, ctypes.byref(total)),
+              "nhip_ms_archive_paths")
+        off = np.zeros(n + 1, dtype=np.uint64)
+        path = np.zeros((max(total.value, 1), 5), dtype=np.uint64)
+        filled = ctypes.c_size_t()
+        check(self.ctx.lib.nhip_ms_archive_paths(self._h, which, _ptr(idx), n, off.ctypes.data, path.ctypes.data,
+                                                 total.value, ctypes.byref(filled)), "nhip_ms_archive_paths")
+        if filled.value != total.value:
+            raise _lib.NhipError("nhip_ms_archive_paths: the count pass and the fill disagree")
+        return off, path[:total.value]
+
+    def _paths(self, which, leaf_indices):
+        off, path = self.paths_raw(which, leaf_indices)
+        return [[tuple(int(x) for x in d) for d in path[int(off[i]):int(off[i + 1])]] for i in range(off.size - 1)]
+
+    def aocl_paths(self, leaf_indices):
+        """`MmrMembershipProof`s of AOCL leaves: a list of digest lists, leaf sibling first."""
+        return self._paths(0, leaf_indices)
+
+    def swbf_paths(self, chunk_indices):
+        return self._paths(1, chunk_indices)
+
+    def leaves(self, which: int, first: int, n: int) -> np.ndarray:
+        """Leaves `first .. first + n - 1` of the AOCL (`which` 0) or of the SWBF MMR (1): n x 5 words."""
+        out = np.zeros((n, 5), dtype=np.uint64)
+        check(self.ctx.lib.nhip_ms_archive_leaves(self._h, which, first, n, _ptr(out)), "nhip_ms_archive_leaves")
+        return out
+
+    def restore_raw(self, index_sets, aocl_leaf_indices):
+        """Both calls of the two-call pattern of `nhip_ms_archive_restore`: `(count-pass totals, output arrays)`."""
+        return _restore_two_calls(lambda mn, dist, li, n, cout: self.ctx.lib.nhip_ms_archive_restore(
+            self._h, _ptr(mn), _ptr(dist), _ptr(li), n, cout), "nhip_ms_archive_restore", index_sets, aocl_leaf_indices)
+
+    def _restore(self, index_sets, aocl_leaf_indices):
+        _, o = self.restore_raw(index_sets, aocl_leaf_indices)
+        dictionaries = unpack_chunks(PackedChunks(o["entry_off"], o["chunk_index"], o["path_off"], o["path"],
+                                                  o["rel_off"], o["rel"]))
+        paths = [[tuple(int(x) for x in d) for d in o["aocl_path"][int(o["aocl_path_off"][i]):int(o["aocl_path_off"][i + 1])]]
+                 for i in range(len(index_sets))]
+        return [int(x) for x in o["status"]], paths, dictionaries
+
+    def restore_membership_proofs(self, items, sender_randomness, receiver_preimages, aocl_leaf_indices):
+        """`ArchivalMutatorSet::restore_membership_proof` (archival_mutator_set.rs:298-346) for many items:
+        `[(status, MsMembershipProof or None)]`.  The index sets are computed on the device
+        (`nhip_absolute_index_sets`)."""
+        n = len(aocl_leaf_indices)
+        if n == 0:
+            return []
+        it, sr, rp = _digests(items, n), _digests(sender_randomness, n), _digests(receiver_preimages, n)
+        leafs = [int(l) for l in aocl_leaf_indices]
+        sets = AbsoluteIndexSet.compute_batch(self.ctx, it, sr, rp, leafs)
+        status, paths, dictionaries = self._restore(sets, leafs)
+        return [(st, None if st != OK else
+                 MsMembershipProof(tuple(int(x) for x in sr[i]), tuple(int(x) for x in rp[i]), paths[i], leafs[i],
+                                   dictionaries[i])) for i, st in enumerate(status)]
+
+    def restore_dictionaries(self, index_sets):
+        """The chunk dictionaries of index sets against the archive's tip: `[(status, target_chunks or None)]`, as
+        the refresh of old removal records needs them (state/archival_state.rs:1156-1179)."""
+        if len(index_sets) == 0:
+            return []
+        status, _, dictionaries = self._restore(list(index_sets), [None] * len(index_sets))
+        return [(st, dictionaries[i] if st == OK else None) for i, st in enumerate(status)]
+
+    def restore_privacy_preserving(self, index_set):
+        """`restore_membership_proof_privacy_preserving` (archival_mutator_set.rs:350-406):
+        `(aocl_auth_paths, dictionary)`, the first a list of `(leaf index, path)` for every leaf index the index set
+        admits (`aocl_range`, clipped to the leaf count), the second its `target_chunks`.  ValueError where the
+        reference returns an error: a range that begins past the AOCL, an index set outside what the archive serves."""
+        lo, hi = aocl_range(index_set)
+        n = self.counts()[0]
+        if lo >= n:
+            raise ValueError("RequestedAoclAuthPathOutOfBounds")
+        (status, dictionary), = self.restore_dictionaries([index_set])
+        if status != OK:
+            raise ValueError(status_name(status))
+        leafs = list(range(lo, min(hi, n - 1) + 1))
+        return list(zip(leafs, self.aocl_paths(leafs))), dictionary
+
+
+def _restore_two_calls(call, name, index_sets, aocl_leaf_indices):
+    n = len(index_sets)
+
+    class _S:  # _index_arrays reads `.absolute_indices`
+        def __init__(self, s):
+            self.absolute_indices = s
+    mn, dist = _index_arrays([_S(s) for s in index_sets])
+    li = np.asarray([2 ** 64 - 1 if l is None else int(l) for l in aocl_leaf_indices], dtype=np.uint64)
+    cout = _lib.MsUpdated()
+    check(call(mn, dist, li, n, ctypes.byref(cout)), name)
+    totals = tuple(int(getattr(cout, f)) for f in ("aocl_digests", "entries", "path_digests", "rel_words"))
+    A, E, PD, RW = totals
+    z = lambda dtype, *shape: np.zeros(shape, dtype=dtype)  # noqa: E731
+    o = dict(status=z(np.uint8, n), aocl_path_off=z(np.uint64, n + 1), aocl_path=z(np.uint64, A, 5),
+             entry_off=z(np.uint64, n + 1), chunk_index=z(np.uint64, E), path_off=z(np.uint64, E + 1),
+             path=z(np.uint64, PD, 5), rel_off=z(np.uint64, E + 1), rel=z(np.uint32, RW))
+    pad = {f: (a if a.size else np.zeros(1, dtype=a.dtype)) for f, a in o.items()}
+    cout = _lib.MsUpdated(*(pad[f].ctypes.data for f, _ in _lib.MsUpdated._fields_[:9]), A, E, PD, RW)
+    check(call(mn, dist, li, n, ctypes.byref(cout)), name)
+    filled = tuple(int(getattr(cout, f)) for f in ("aocl_digests", "entries", "path_digests", "rel_words"))
+    if filled != totals:
+        raise _lib.NhipError(name + ": the count pass and the fill disagree")
+    return totals, o
+
+
+def restore_plan(aocl_leafs: int, chunk_lengths, index_sets, aocl_leaf_indices):
+    """The host half of `Archive.restore_*` (no GPU, `nhip_ms_archive_restore_plan`): `(totals, output arrays)` with
+    the statuses, the offset arrays and the keys; digests and chunk words stay zero."""
+    lens = np.ascontiguousarray(np.asarray(list(chunk_lengths), dtype=np.uint64))
+    lib = _lib.load()
+    return _restore_two_calls(lambda mn, dist, li, n, cout: lib.nhip_ms_archive_restore_plan(
+        int(aocl_leafs), _ptr(lens), lens.size, _ptr(mn), _ptr(dist), _ptr(li), n, cout),
+        "nhip_ms_archive_restore_plan", index_sets, aocl_leaf_indices)

@@ -31,7 +31,7 @@ macro_rules! opaque {
     ($($name:ident),*) => { $( #[repr(C)] pub struct $name { _p: [u8; 0] } )* };
 }
 opaque!(nhip_ctx, nhip_air, nhip_batch, nhip_group, nhip_group_stream, nhip_queue, nhip_pow_buffer, nhip_arena,
-        nhip_ms_store);
+        nhip_ms_store, nhip_ms_archive);
 
 /// `Stark::default()` plus the table dimensions (`nhip_stark_params_default`).
 #[repr(C)]
@@ -323,6 +323,19 @@ pub struct nhip_ms_store_caps {
     pub aocl_digests: usize,
     pub entries: usize,
     pub path_digests: usize,
+    pub rel_words: usize,
+}
+
+/// Load gives a level of an archive's MMRs a launch of its own while the level below has more nodes than this
+/// (`NHIP_MS_ARCHIVE_TAIL_NODES`).
+pub const NHIP_MS_ARCHIVE_TAIL_NODES: usize = 256;
+
+/// Initial capacities of a device-resident archival mutator set (`nhip_ms_archive_create`; 0: a default).
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct nhip_ms_archive_caps {
+    pub aocl_leafs: usize,
+    pub chunks: usize,
     pub rel_words: usize,
 }
 
@@ -692,6 +705,26 @@ extern "C" {
     pub fn nhip_ms_store_retain(store: *mut nhip_ms_store, keep: *const u8) -> c_int;
     pub fn nhip_ms_store_check(store: *mut nhip_ms_store, msa: *const nhip_msa, aocl_member: *mut u8, valid: *mut u8,
                                can_remove: *mut u8, status: *mut u8) -> c_int;
+    pub fn nhip_ms_archive_create(ctx: *mut nhip_ctx, initial: *const nhip_ms_archive_caps,
+                                  out: *mut *mut nhip_ms_archive) -> c_int;
+    pub fn nhip_ms_archive_destroy(archive: *mut nhip_ms_archive);
+    pub fn nhip_ms_archive_count(archive: *const nhip_ms_archive, aocl_leafs: *mut u64, chunks: *mut u64,
+                                 n_active: *mut u64, rel_live: *mut u64, rel_dead: *mut u64) -> c_int;
+    pub fn nhip_ms_archive_load(archive: *mut nhip_ms_archive, aocl_leaves: *const u64, n_leafs: u64,
+                                rel_off: *const u64, rel: *const u32, n_chunks: u64, active: *const u32,
+                                n_active: u64) -> c_int;
+    pub fn nhip_ms_archive_accumulator(archive: *mut nhip_ms_archive, out: *mut nhip_ms_apply_out) -> c_int;
+    pub fn nhip_ms_archive_apply(archive: *mut nhip_ms_archive, block: *const nhip_ms_apply_in,
+                                 block_out: *mut nhip_ms_apply_out) -> c_int;
+    pub fn nhip_ms_archive_paths(archive: *mut nhip_ms_archive, which: c_int, leaf_index: *const u64, n: usize,
+                                 path_off: *mut u64, path: *mut u64, path_cap: usize, path_digests: *mut usize) -> c_int;
+    pub fn nhip_ms_archive_leaves(archive: *mut nhip_ms_archive, which: c_int, first: u64, n: u64,
+                                  out: *mut u64) -> c_int;
+    pub fn nhip_ms_archive_restore(archive: *mut nhip_ms_archive, minimum: *const u64, distances: *const u32,
+                                   aocl_leaf_index: *const u64, n: usize, out: *mut nhip_ms_updated) -> c_int;
+    pub fn nhip_ms_archive_restore_plan(aocl_leafs: u64, chunk_len: *const u64, n_chunks: u64, minimum: *const u64,
+                                        distances: *const u32, aocl_leaf_index: *const u64, n: usize,
+                                        out: *mut nhip_ms_updated) -> c_int;
     pub fn nhip_blk_ms_params_default(out: *mut nhip_blk_ms_params);
     pub fn nhip_blk_ms_walk(bytes: *const u8, n_bytes: usize, pow_tree_height: u32, blocks: *const nhip_blk_block,
                             n: usize, out: *mut nhip_blk_ms_parts) -> c_int;
