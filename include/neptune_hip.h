@@ -1057,6 +1057,35 @@ int nhip_ms_archive_accumulator(nhip_ms_archive *archive, nhip_ms_apply_out *out
  * device; all allocation and growth precede the first launch that writes archive state, and the mirror and the counts
  * advance only after the stream drains clean.  Afterwards nhip_ms_archive_accumulator equals what block_out reported. */
 int nhip_ms_archive_apply(nhip_ms_archive *archive, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out);
+/* The way back when the tip moves to another fork: ArchivalState::update_mutator_set's walk over an abandoned block
+ * (state/archival_state.rs:1293-1335: revert_remove per removal record, then add_is_reversible / revert_add per
+ * addition in reverse, archival_mutator_set.rs:417-490) as an end state.  The archive stands at the accumulator after
+ * `block` and is taken to block->msa_before[0].  With n1 / b1 the archive's AOCL leaf and chunk counts, k additions,
+ * n0 = n1 - k and b0 = batch_index(n0): the AOCL keeps its first n0 leaves and no node is hashed; the chunks [b0, b1)
+ * are dropped; every chunk below b0 that a block index hits loses one copy of that index per occurrence the block
+ * inserted (Chunk::subtract) and is written anew at the arena's tail, its old words dead; the rewritten chunks are
+ * hashed and every SWBF node above one that exists at b0 is hashed again; the window becomes msa_before's.  Dead words
+ * count and the arena compacts as after an apply; no capacity shrinks.
+ *   1. block->n_jobs == 1 and the accumulator outputs of block_out present, else NHIP_ERR_ARG.
+ *   2. The tip check, before anything is written: steps 1-5 of nhip_ms_apply_batch run on (msa_before, block), decide
+ *      rules 2.b-2.e (a msa_expected is honoured) and fill block_out.  If the job ends NHIP_MS_OK, the accumulator it
+ *      computed has to be the archive's own: both counts and the window word for word (against the mirror), both peak
+ *      lists (against the level arrays).  Any difference, or counts no block can have led to, is
+ *      NHIP_MS_UPDATE_MISMATCH ("this block did not lead to this tip"), reported as a 2.e failure is: verdict 0,
+ *      bad_record UINT64_MAX.  Unless the job ends NHIP_MS_OK and the tip matches, the archive is unchanged in every
+ *      count and byte a later call can observe.
+ *   3. All allocation (arena growth for the tail writes, a longer window, the compaction's buffers) precedes the first
+ *      launch that writes archive state; an error there leaves the archive as it was.
+ *   4. The mirror and the counts move only after the stream drains clean; a HIP error behind a write poisons the archive.
+ *   5. Never a guess: the subtraction flags a chunk that holds fewer copies of a block index than the block inserted,
+ *      and after the writes the peaks are read back and compared with msa_before's at n0 and b0 (the reference's
+ *      closing sanity assert), both on the drain that is due anyway.  A set flag or a difference poisons the archive
+ *      and returns NHIP_ERR_HIP; nothing is reported as reverted.
+ *   6. A block of 0 additions and 0 records is NHIP_MS_OK and changes nothing if the tip matches; a revert down to
+ *      n0 == 0 leaves an empty archive that nhip_ms_archive_load accepts again.
+ * On NHIP_MS_OK block_out holds the accumulator after the block, as nhip_ms_apply_batch fills it, and
+ * nhip_ms_archive_accumulator equals msa_before. */
+int nhip_ms_archive_revert(nhip_ms_archive *archive, const nhip_ms_apply_in *block, nhip_ms_apply_out *block_out);
 /* ArchivalMmr::prove_membership_async (archival_mmr.rs:297-321) for n leaves of one MMR (which: 0 AOCL, 1 SWBF):
  * path_off n + 1, in digests.  Two-call sizing: with path_off and path NULL only *path_digests is written (from the
  * mirror alone); otherwise path_cap >= the total, else NHIP_ERR_ARG.  An index >= the leaf count is NHIP_ERR_ARG with

@@ -266,6 +266,78 @@ void ms_archive_compact_commit(MsArchiveMirror& m) {
     m.rel_tail = m.rel_live = at;
 }
 
+int ms_archive_revert_plan(const MsArchiveMirror& m, uint64_t additions, const uint64_t* minimum, const uint32_t* distances,
+                           size_t records, MsArchRevertPlan* plan) {
+    if (records > 0xFFFFFFFFull / NUM_TRIALS) return NHIP_ERR_OOM;
+    if (records && (!minimum || !distances)) return NHIP_ERR_ARG;
+    if (additions > m.aocl_leafs) return MS_ARCHIVE_REVERT_IMPOSSIBLE;
+    MsArchRevertPlan p;
+    p.n1 = m.aocl_leafs;
+    p.n0 = p.n1 - additions;
+    p.b0 = MsJobScratch::batch_index(p.n0);
+    p.b1 = m.chunks();
+    if (p.b0 > p.b1) return MS_ARCHIVE_REVERT_IMPOSSIBLE;
+    // the block's indices below b0, as (chunk, relative) sorted; those from b0 on lie in chunks that are dropped or in
+    // the window, which is replaced whole
+    std::vector<std::pair<uint64_t, uint32_t>> hits;
+    for (size_t r = 0; r < records; ++r) {
+        const u128 mn = ((u128)minimum[2 * r + 1] << 64) | minimum[2 * r];
+        for (uint32_t t = 0; t < NUM_TRIALS; ++t) {
+            const u128 index = mn + distances[(size_t)NUM_TRIALS * r + t];
+            if (index < mn || (index >> CHUNK_BITS) >= (u128)p.b0) continue;
+            hits.emplace_back((uint64_t)(index >> CHUNK_BITS), (uint32_t)index & (MS_ARCHIVE_CHUNK_SIZE - 1));
+        }
+    }
+    std::sort(hits.begin(), hits.end());
+    p.block_rel.reserve(hits.size());
+    for (const auto& h : hits) p.block_rel.push_back(h.second);
+    uint64_t tail = m.rel_tail, live = m.rel_live;
+    for (size_t i = 0; i < hits.size();) {
+        size_t j = i;
+        while (j < hits.size() && hits[j].first == hits[i].first) ++j;
+        MsArchWritten w{};
+        w.c = hits[i].first;  // < b0 <= b1: inside the mirror's table
+        w.a_off = m.chunk_off[(size_t)w.c];
+        w.a_len = m.chunk_len[(size_t)w.c];
+        w.b_off = i;
+        w.b_len = j - i;
+        if (w.a_len < w.b_len) return MS_ARCHIVE_REVERT_IMPOSSIBLE;
+        w.out_off = tail;
+        tail += w.a_len - w.b_len;
+        if (tail < w.out_off || tail > MS_ARCHIVE_LIMIT || live < w.b_len) return NHIP_ERR_OOM;
+        live -= w.b_len;  // the old copy dies, the new one is that much shorter
+        p.rewritten.push_back(w);
+        i = j;
+    }
+    for (uint64_t c = p.b0; c < p.b1; ++c) p.dropped_words += m.chunk_len[(size_t)c];
+    if (live < p.dropped_words) return NHIP_ERR_OOM;  // a mirror whose live count is not the sum of its lengths
+    live -= p.dropped_words;
+    p.rel_tail_after = tail;
+    p.rel_live_after = live;
+    p.compact = tail - live > live;
+    std::vector<uint64_t> leafs;
+    for (const MsArchWritten& w : p.rewritten) leafs.push_back(w.c);
+    ancestors(leafs, p.b0, &p.ids, &p.lvl_off);
+    *plan = std::move(p);
+    return NHIP_OK;
+}
+
+void ms_archive_revert_commit(MsArchiveMirror& m, const MsArchRevertPlan& plan, const uint32_t* active, uint64_t n_active) {
+    std::vector<uint64_t> off(m.chunk_off.begin(), m.chunk_off.begin() + (size_t)plan.b0);
+    std::vector<uint64_t> len(m.chunk_len.begin(), m.chunk_len.begin() + (size_t)plan.b0);
+    for (const MsArchWritten& w : plan.rewritten) {
+        off[(size_t)w.c] = w.out_off;
+        len[(size_t)w.c] = w.a_len - w.b_len;
+    }
+    std::vector<uint32_t> window(active, active + (size_t)n_active);
+    m.aocl_leafs = plan.n0;
+    m.chunk_off = std::move(off);
+    m.chunk_len = std::move(len);
+    m.window = std::move(window);
+    m.rel_tail = plan.rel_tail_after;
+    m.rel_live = plan.rel_live_after;
+}
+
 size_t ms_archive_grown(size_t cap, size_t need, size_t limit) {
     if (need > limit) return 0;
     if (need <= cap) return cap;

@@ -24,6 +24,11 @@ static constexpr uint32_t MS_ARCHIVE_CHUNK_SIZE = 1u << 12, MS_ARCHIVE_WINDOW_SI
 // [k 2^h, (k + 1) 2^h) and exists iff (k + 1) 2^h <= n.  The levels lie in one array of 2 cap digests, cap a power of
 // two >= n: level h has cap >> h slots from digest 2 cap - (2 cap >> h) on, so the address of a node is arithmetic on
 // (h, k) alone.  Levels above ilog2(cap) hold nothing.
+// A revert (ms_archive_revert_plan) takes n down to n0 and hashes no AOCL node: a node that exists at n0 has only old
+// leaves below it, and no apply since wrote it.  The slots at or beyond n0 >> h of level h are stale from then on and
+// nothing may read them (every reader addresses existing nodes only: paths, peaks, the copies of a growth); the next
+// apply lists every node above a new leaf (MsArchApplyPlan::ids), so it overwrites a stale slot before the leaf count
+// makes it visible.  The same holds for the SWBF MMR at b0, whose nodes above a rewritten chunk are hashed again.
 NHIP_MS_HD uint64_t ms_arch_level_base(uint64_t cap, uint32_t h) { return 2 * cap - ((2 * cap) >> h); }  // h <= ilog2(cap) + 1
 NHIP_MS_HD uint64_t ms_arch_node(uint64_t cap, uint32_t h, uint64_t k) { return ms_arch_level_base(cap, h) + k; }
 NHIP_MS_HD uint32_t ms_arch_ilog2(uint64_t x) {  // x != 0
@@ -116,6 +121,37 @@ void ms_archive_apply_commit(MsArchiveMirror& m, const MsArchApplyPlan& plan, co
                              uint64_t aocl_cap, uint64_t swbf_cap);
 // the arena after a compaction: chunk c's words at the exclusive scan of the lengths
 void ms_archive_compact_commit(MsArchiveMirror& m);
+
+// ---- revert: the archive back across the block it stands behind, as an end state (ArchivalState::update_mutator_set's
+// walk over abandoned blocks: revert_remove per record, then add_is_reversible / revert_add per addition in reverse).
+// With n1 / b1 the mirror's counts, n0 = n1 - additions and b0 = batch_index(n0): the AOCL keeps its first n0 leaves
+// (no node is hashed); the chunks [b0, b1) are dropped; every chunk below b0 that a block index hits loses one copy of
+// that index per occurrence the block inserted (Chunk::subtract, the inverse of the apply plan's "repeats kept") and is
+// written anew at the arena's tail; the SWBF MMR gets those leaves and every node above them that exists at b0.
+// `rewritten` reuses MsArchWritten, the one layout the kernels read: a_off / a_len the chunk's words now, b_off / b_len
+// the block's sorted relative indices in it, out_off where its a_len - b_len words after go; a_sub and from_window 0.
+struct MsArchRevertPlan {
+    uint64_t n0 = 0, n1 = 0, b0 = 0, b1 = 0;
+    std::vector<MsArchWritten> rewritten;  // ascending in c, all below b0
+    std::vector<uint32_t> block_rel;
+    uint64_t dropped_words = 0;  // of the chunks [b0, b1), which leave the table
+    uint64_t rel_tail_after = 0, rel_live_after = 0;
+    // the SWBF nodes to hash again, as MsArchApplyPlan::ids[1] / lvl_off[1]: a node is listed iff it exists at b0 and a
+    // rewritten chunk lies below it
+    std::vector<uint64_t> ids;
+    std::vector<uint32_t> lvl_off;
+    bool compact = false;  // dead words exceed live words after the revert
+};
+// beside the NHIP_* codes: no block of these additions and records can have led to the mirror (additions > aocl_leafs,
+// batch_index(n0) > chunks, or a hit chunk with fewer words than block indices in it); *plan is left alone
+static constexpr int MS_ARCHIVE_REVERT_IMPOSSIBLE = -1;
+// The plan is total: any additions, any records (null arrays with records == 0), any mirror whose two chunk vectors
+// have one length.  NHIP_ERR_ARG: records without their arrays; NHIP_ERR_OOM past the limits.  May throw std::bad_alloc.
+int ms_archive_revert_plan(const MsArchiveMirror& m, uint64_t additions, const uint64_t* minimum, const uint32_t* distances,
+                           size_t records, MsArchRevertPlan* plan);
+// the mirror after a revert whose plan this is and whose window before the block is `active` (sorted); capacities stay;
+// throws before it changes anything
+void ms_archive_revert_commit(MsArchiveMirror& m, const MsArchRevertPlan& plan, const uint32_t* active, uint64_t n_active);
 // capacities: at least need, at least double cap (ms_store_grown's rule); 0 past limit
 size_t ms_archive_grown(size_t cap, size_t need, size_t limit);
 

@@ -107,6 +107,47 @@ struct GatherPlan {
     nhip::MsArchGatherDev g{};
 };
 
+// The arena's compaction behind an apply or a revert that leaves more dead words than live ones: one gather of every
+// chunk into a second arena (`spare`, rel_live words) and the table of that arena (d_tab2); the caller swaps both in.
+struct Compaction {
+    std::vector<uint64_t> scan, tab2;
+    nhip::MsArchUnits units;
+    // after: the mirror behind the call's writes, before ms_archive_compact_commit
+    void plan(const nhip::MsArchiveMirror& after) {
+        const size_t n = (size_t)after.chunks();
+        scan.assign(n + 1, 0);
+        for (size_t k = 0; k < n; ++k) scan[k + 1] = scan[k] + after.chunk_len[k];
+        units = nhip::ms_arch_units(scan.data(), n, 1, true);
+        tab2.resize(2 * n);
+        for (size_t k = 0; k < n; ++k) tab2[2 * k] = scan[k], tab2[2 * k + 1] = after.chunk_len[k];
+    }
+    bool moves() const { return !scan.empty() && scan.back() != 0; }  // no live word: nothing to gather
+    // behind a drained stream (the plan's device arrays are no longer needed): a small phase with buffers of its own
+    int run(Stage& st, nhip_ctx* c, const uint64_t* d_tab, const uint32_t* d_arena, uint32_t* spare, uint64_t* d_tab2) {
+        if (!moves()) return NHIP_OK;
+        uint64_t* d_scan = nullptr;
+        uint32_t* d_first = nullptr;
+        int rc;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_scan), 8 * scan.size());
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_first), 4 * units.first.size());
+        if (e == hipSuccess) {
+            st.up(d_scan, scan.data(), scan.size());
+            st.up(d_first, units.first.data(), units.first.size());
+            nhip::MsArchGatherDev g{};
+            g.rel.tab = d_tab, g.rel.arena = d_arena, g.rel.key = nullptr, g.rel.dst_off = d_scan;
+            g.rel.owners = scan.size() - 1, g.rel.units = units.units, g.rel.first = d_first, g.rel.dst = spare;
+            st.launch([&] { return nhip::launch_ms_arch_gather(g, c->stream); });
+            st.up(d_tab2, tab2.data(), tab2.size());
+            rc = st.finish();
+        } else {
+            rc = nhip::hip_fail(e);
+        }
+        if (d_scan) (void)hipFree(d_scan);
+        if (d_first) (void)hipFree(d_first);
+        return rc;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -438,38 +479,10 @@ int nhip_ms_archive_apply(nhip_ms_archive* a, const nhip_ms_apply_in* block, nhi
         const uint32_t levels[2] = {(uint32_t)plan.lvl_off[0].size() - 1, (uint32_t)plan.lvl_off[1].size() - 1};
         st.launch([&] { return nhip::launch_ms_arch_ancestors(lv, d_ids, d_off, levels, c->stream); });
         st.up(d_window, active_after, (size_t)n_after);
-        std::vector<uint64_t> tab2;
-        nhip::MsArchUnits units;
-        std::vector<uint64_t> scan;
-        if (plan.compact) {  // one gather of every chunk into the second arena, then the two are swapped
-            scan.assign((size_t)plan.b1 + 1, 0);
-            for (size_t k = 0; k < (size_t)plan.b1; ++k) scan[k + 1] = scan[k] + after.chunk_len[k];
-            units = nhip::ms_arch_units(scan.data(), (size_t)plan.b1, 1, true);
-        }
+        Compaction compaction;
+        if (plan.compact) compaction.plan(after);
         rc = st.finish();
-        if (rc == NHIP_OK && plan.compact && scan.back()) {
-            // the plan's device arrays are no longer needed: a second, small phase with buffers of its own
-            uint64_t* d_scan = nullptr;
-            uint32_t* d_first = nullptr;
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_scan), 8 * scan.size());
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_first), 4 * units.first.size());
-            if (e == hipSuccess) {
-                st.up(d_scan, scan.data(), scan.size());
-                st.up(d_first, units.first.data(), units.first.size());
-                nhip::MsArchGatherDev g{};
-                g.rel.tab = d_tab, g.rel.arena = d_arena, g.rel.key = nullptr, g.rel.dst_off = d_scan;
-                g.rel.owners = plan.b1, g.rel.units = units.units, g.rel.first = d_first, g.rel.dst = spare.p;
-                st.launch([&] { return nhip::launch_ms_arch_gather(g, c->stream); });
-                tab2.resize(2 * (size_t)plan.b1);
-                for (size_t k = 0; k < (size_t)plan.b1; ++k) tab2[2 * k] = scan[k], tab2[2 * k + 1] = after.chunk_len[k];
-                st.up(d_tab2, tab2.data(), tab2.size());
-                rc = st.finish();
-            } else {
-                rc = nhip::hip_fail(e);
-            }
-            if (d_scan) (void)hipFree(d_scan);
-            if (d_first) (void)hipFree(d_first);
-        }
+        if (rc == NHIP_OK && plan.compact) rc = compaction.run(st, c, d_tab, d_arena, spare.p, d_tab2);
         if (d_old_window) (void)hipFree(d_old_window);
         if (rc != NHIP_OK) {
             fresh.take();  // what the launches wrote into; nothing is read from it again
@@ -478,12 +491,158 @@ int nhip_ms_archive_apply(nhip_ms_archive* a, const nhip_ms_apply_in* block, nhi
         }
         fresh.take();
         if (plan.compact) {
-            if (scan.back()) {
+            if (compaction.moves()) {
                 a->arena.release();
                 a->arena.p = spare.p, a->arena.cap = std::max<size_t>((size_t)plan.rel_live_after, 1);
                 spare.p = nullptr;
                 a->tab.release();
                 a->tab.p = d_tab2, a->tab.cap = std::max<size_t>(2 * (size_t)plan.b1, 1);
+                d_tab2 = nullptr;
+            }
+            nhip::ms_archive_compact_commit(after);
+        }
+        bail(NHIP_OK);
+        m = std::move(after);
+        return NHIP_OK;
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// ArchivalState::update_mutator_set's walk back over an abandoned block as an end state (MsArchRevertPlan).  The block
+// runs through the block part on (msa_before, block); the accumulator it computes has to be the archive's own (the tip
+// check) before anything is written.  Then the rewritten chunks lose the block's indices at the arena's tail, are
+// hashed, the SWBF nodes above them that exist at b0 are hashed again, the window before is uploaded, and the peaks at
+// (n0, b0) are read back against msa_before's together with the kernel's short-of flag.
+int nhip_ms_archive_revert(nhip_ms_archive* a, const nhip_ms_apply_in* block, nhip_ms_apply_out* block_out) {
+    nhip::MsApplyCounts cnt;
+    if (!a || !block || block->n_jobs != 1 || nhip::ms_apply_ok(block, block_out, &cnt) || !cnt.accumulators) return NHIP_ERR_ARG;
+    nhip_ctx* c = a->c;
+    try {
+        Stage st(c);
+        if (a->poisoned) return NHIP_ERR_HIP;
+        nhip::MsArchiveMirror& m = a->m;
+        const nhip_msa& before = block->msa_before[0];
+        nhip::MsArchRevertPlan plan;
+        int rc = nhip::ms_archive_revert_plan(m, cnt.additions, block->minimum, block->distances, (size_t)cnt.records, &plan);
+        const bool impossible = rc == nhip::MS_ARCHIVE_REVERT_IMPOSSIBLE;  // reported behind the block part's own status
+        if (rc != NHIP_OK && !impossible) return rc;
+        const size_t NR = plan.rewritten.size();
+        std::vector<uint32_t> window_before;
+        nhip::ms_append_sorted_window(window_before, before);
+        const bool have_nodes = !m.empty() && a->nodes[0].p && a->nodes[1].p;
+        BlockPart blk(*block, *block_out, cnt, false);
+        const nhip::MsArchWritten* d_rewritten;
+        const uint32_t *d_block_rel, *d_off;
+        const uint64_t* d_ids;
+        uint64_t* d_peaks;  // the tip's, then those after the writes
+        uint32_t* d_short_of;
+        const uint32_t zero = 0;
+        uint32_t short_of = 0;
+        std::vector<uint64_t> peaks(2 * 64 * 5, 0), peaks_after(2 * 64 * 5, 0);
+        blk.declare(st);
+        st.in(d_rewritten, plan.rewritten.data(), NR);
+        st.in(d_block_rel, plan.block_rel.data(), plan.block_rel.size());
+        st.in(d_ids, plan.ids.data(), plan.ids.size());
+        st.in(d_off, plan.lvl_off.data(), plan.lvl_off.size());
+        st.in(d_short_of, &zero, 1);
+        st.tmp(d_peaks, 4 * 64, 5);
+        if (st.commit()) return st.finish();
+        blk.enqueue(st, c);
+        blk.read_back(st);
+        if (have_nodes) {
+            const nhip::MsArchLevels lv[2] = {a->levels(0), a->levels(1)};
+            st.launch([&] { return nhip::launch_ms_arch_peaks(lv, d_peaks, c->stream); });
+            st.out(peaks.data(), d_peaks, peaks.size());
+        }
+        if ((rc = st.finish()) != NHIP_OK) return rc;  // nothing of the archive was written
+        blk.write_outputs();
+        if (block_out->status[0] != NHIP_MS_OK) return NHIP_OK;  // a rule of the block: the archive stays as it was
+        // ---- the tip check: the accumulator after the block against the archive's own, the counts and the window
+        // against the mirror, the peaks against the device's; and msa_before against the plan's counts
+        const uint32_t np1[2] = {(uint32_t)__builtin_popcountll(m.aocl_leafs), (uint32_t)__builtin_popcountll(m.chunks())};
+        const uint32_t* tip_active = block_out->active + block_out->active_off[0];
+        bool tip = !impossible && block_out->aocl_num_leafs[0] == m.aocl_leafs && block_out->swbf_num_leafs[0] == m.chunks() &&
+                   block_out->aocl_n_peaks[0] == np1[0] && block_out->swbf_n_peaks[0] == np1[1] &&
+                   block_out->n_active[0] == m.window.size() && std::equal(m.window.begin(), m.window.end(), tip_active);
+        if (tip)
+            tip = std::equal(block_out->aocl_peaks, block_out->aocl_peaks + 5 * (size_t)np1[0], peaks.begin()) &&
+                  std::equal(block_out->swbf_peaks, block_out->swbf_peaks + 5 * (size_t)np1[1], peaks.begin() + 320);
+        const uint32_t np0[2] = {(uint32_t)__builtin_popcountll(plan.n0), (uint32_t)__builtin_popcountll(plan.b0)};
+        if (tip)
+            tip = before.aocl.num_leafs == plan.n0 && before.swbf_inactive.num_leafs == plan.b0 && before.aocl.n_peaks == np0[0] &&
+                  before.swbf_inactive.n_peaks == np0[1];
+        if (!tip) {  // this block did not lead to this tip: as nhip_ms_apply_batch reports a 2.e failure
+            block_out->verdict[0] = 0;
+            block_out->status[0] = NHIP_MS_UPDATE_MISMATCH;
+            block_out->bad_record[0] = UINT64_MAX;
+            return NHIP_OK;
+        }
+        // ---- all allocation and growth before the first launch that writes archive state: host memory, then device
+        nhip::MsArchiveMirror after = m;
+        nhip::ms_archive_revert_commit(after, plan, window_before.data(), window_before.size());
+        Compaction compaction;
+        if (plan.compact) compaction.plan(after);
+        Fresh fresh;
+        uint32_t *d_arena, *d_window;
+        bool arena_grown;
+        if ((rc = fresh.want(a->arena, (size_t)plan.rel_tail_after, &d_arena, &arena_grown)) != NHIP_OK) return rc;
+        if ((rc = fresh.want(a->window, window_before.size(), &d_window)) != NHIP_OK) return rc;
+        Arr<uint32_t> spare;  // the second arena of a compaction, and its table (of the table's capacity: none shrinks)
+        uint64_t* d_tab2 = nullptr;
+        const size_t tab_cap = std::max<size_t>(a->tab.cap, 1);
+        if (plan.compact) {
+            hipError_t e = hipMalloc(reinterpret_cast<void**>(&spare.p), std::max<size_t>((size_t)plan.rel_live_after, 1) * 4);
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_tab2), tab_cap * 8);
+            if (e != hipSuccess) {
+                spare.release();
+                return nhip::hip_fail(e);
+            }
+        }
+        auto bail = [&](int code) {
+            spare.release();
+            if (d_tab2) (void)hipFree(d_tab2);
+            return code;
+        };
+        if (arena_grown && a->arena.p && m.rel_tail) {
+            st.step([&] {
+                return nhip::hip_fail(hipMemcpyAsync(d_arena, a->arena.p, 4 * (size_t)m.rel_tail, hipMemcpyDeviceToDevice, c->stream));
+            });
+            if ((rc = st.finish()) != NHIP_OK) return bail(rc);  // the fresh buffers are dropped, the archive is as it was
+        }
+        // ---- from here on the archive is written: a HIP error poisons it
+        const nhip::MsArchLevels lv[2] = {{a->nodes[0].p, m.aocl_cap, plan.n0}, {a->nodes[1].p, m.swbf_cap, plan.b0}};
+        st.launch([&] { return nhip::launch_ms_arch_unmerge(d_rewritten, NR, d_block_rel, d_arena, a->tab.p, d_short_of, c->stream); });
+        st.launch([&] { return nhip::launch_ms_arch_chunk_digests(a->tab.p, d_arena, 0, NR, d_rewritten, lv[1], c->stream); });
+        const uint64_t* const ids2[2] = {nullptr, d_ids};
+        const uint32_t* const off2[2] = {nullptr, d_off};
+        const uint32_t levels[2] = {0, plan.lvl_off.empty() ? 0u : (uint32_t)plan.lvl_off.size() - 1};  // no AOCL node is hashed
+        st.launch([&] { return nhip::launch_ms_arch_ancestors(lv, ids2, off2, levels, c->stream); });
+        st.up(d_window, window_before.data(), window_before.size());
+        // never a guess: the peaks at (n0, b0) against msa_before's and the short-of flag, on the drain that is due anyway
+        if (have_nodes) {
+            st.launch([&] { return nhip::launch_ms_arch_peaks(lv, d_peaks + 2 * 64 * 5, c->stream); });
+            st.out(peaks_after.data(), d_peaks, peaks_after.size(), 2 * 64 * 5);
+        }
+        st.out(&short_of, d_short_of, 1);
+        rc = st.finish();
+        if (rc == NHIP_OK &&
+            (short_of || !std::equal(before.aocl.peaks, before.aocl.peaks + 5 * (size_t)np0[0], peaks_after.begin()) ||
+             !std::equal(before.swbf_inactive.peaks, before.swbf_inactive.peaks + 5 * (size_t)np0[1], peaks_after.begin() + 320)))
+            rc = NHIP_ERR_HIP;  // the reference's closing sanity assert: nothing is reported as reverted
+        if (rc == NHIP_OK && plan.compact) rc = compaction.run(st, c, a->tab.p, d_arena, spare.p, d_tab2);
+        fresh.take();  // on an error: what the launches wrote into; nothing is read from it again
+        if (rc != NHIP_OK) {
+            a->poisoned = true;
+            return bail(rc);
+        }
+        if (plan.compact) {
+            if (compaction.moves()) {
+                a->arena.release();
+                a->arena.p = spare.p, a->arena.cap = std::max<size_t>((size_t)plan.rel_live_after, 1);
+                spare.p = nullptr;
+                a->tab.release();
+                a->tab.p = d_tab2, a->tab.cap = tab_cap;
                 d_tab2 = nullptr;
             }
             nhip::ms_archive_compact_commit(after);

@@ -50,7 +50,12 @@ hipError_t launch_ms_arch_chunk_digests(const uint64_t* d_tab, const uint32_t* d
 // apply: the n written chunks merged to the arena's tail and their table entries (MsArchWritten, ms_archive.hpp)
 hipError_t launch_ms_arch_chunks(const MsArchWritten* d_written, uint64_t n, const uint32_t* d_block_rel,
                                  const uint32_t* d_window, uint32_t* d_arena, uint64_t* d_tab, hipStream_t st);
-// apply: per MMR the nodes ids[off[h - 1] .. off[h]) of level h = 1 .. levels hashed again (MsArchApplyPlan)
+// revert: the n rewritten chunks minus the block's indices to the arena's tail and their table entries
+// (MsArchRevertPlan::rewritten); *d_short_of, zero before, becomes 1 if a chunk holds fewer copies of a block index
+// than the block inserted
+hipError_t launch_ms_arch_unmerge(const MsArchWritten* d_rewritten, uint64_t n, const uint32_t* d_block_rel, uint32_t* d_arena,
+                                  uint64_t* d_tab, uint32_t* d_short_of, hipStream_t st);
+// apply, revert: per MMR the nodes ids[off[h - 1] .. off[h]) of level h = 1 .. levels hashed again (MsArchApplyPlan)
 hipError_t launch_ms_arch_ancestors(const MsArchLevels m[2], const uint64_t* const d_ids[2], const uint32_t* const d_off[2],
                                     const uint32_t levels[2], hipStream_t st);
 // d_out: 2 x 64 digests, the peaks of m[0] then of m[1], tallest first, zero behind the last

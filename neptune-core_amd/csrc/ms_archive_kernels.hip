@@ -16,8 +16,10 @@
 //                            height h is node (h, (n >> h) - 1).
 //  k_ms_arch_chunks        : apply.  Eight lanes per chunk written: its words before merged with the block's indices in
 //                            it, at the arena's tail, and its table entry.
-//  k_ms_arch_ancestors     : apply.  One workgroup per MMR hashes every node above a new or changed leaf again, level
-//                            after level from the host plan's lists, out of the archive's own level arrays.
+//  k_ms_arch_unmerge       : revert.  Eight lanes per chunk rewritten: its words minus the block's indices in it (one copy
+//                            per occurrence), at the arena's tail, and its table entry.
+//  k_ms_arch_ancestors     : apply and revert.  One workgroup per MMR hashes every node above a new or changed leaf
+//                            again, level after level from the host plan's lists, out of the archive's own level arrays.
 //  k_ms_arch_gather        : paths, restore and the arena's compaction.  A lane per 8-byte destination word, consecutive lanes storing
 //                            consecutive words, in units of MS_ARCHIVE_GATHER_UNIT words.  Two pools of authentication
 //                            paths and one of chunk words.  Which output range a word belongs to is found as in
@@ -202,6 +204,46 @@ __global__ void __launch_bounds__(ARCH_THREADS) k_ms_arch_chunks(const MsArchWri
     }
 }
 
+// Eight lanes per chunk rewritten: the multiset difference of two sorted lists, the chunk's words now and the block's
+// relative indices in it (Chunk::subtract once per index; the inverse of k_ms_arch_chunks' "repeats kept").  The rule is
+// k_ms_rev_chunks' (ms_revert_kernels.hip), restated: the word at position i, the rank-th of its value, goes if the
+// block inserted more copies than that; a word that stays moves down by the block's indices below it and its own
+// value's copies.  A block value with fewer copies in the chunk than the block inserted sets *short_of, and the host
+// then trusts nothing the call wrote; `pos < out_len` keeps every write inside the planned range even then.  Lane 0 of
+// the eight writes the chunk's table entry.  Reads below the old tail only (a_off + a_len <= old tail <= out_off),
+// writes [out_off, out_off + a_len - b_len) only; the host plan has a_len >= b_len.
+__global__ void __launch_bounds__(ARCH_THREADS) k_ms_arch_unmerge(const MsArchWritten* __restrict__ written, uint64_t n,
+                                                                  const uint32_t* __restrict__ block_rel, uint32_t* arena,
+                                                                  uint64_t* __restrict__ tab, uint32_t* __restrict__ short_of) {
+    const uint32_t sub = threadIdx.x & 7u;
+    for (uint64_t i = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 3; i < n; i += ((uint64_t)gridDim.x * blockDim.x) >> 3) {
+        const MsArchWritten w = written[i];
+        const uint32_t* a = arena + w.a_off;
+        const uint32_t* b = block_rel + w.b_off;
+        uint32_t* out = arena + w.out_off;
+        const uint64_t out_len = w.a_len - w.b_len;
+        for (uint64_t k = sub; k < w.a_len; k += 8) {
+            const uint32_t v = a[k];
+            const uint64_t rank = k - lb_u32(a, w.a_len, v);
+            const uint64_t lt = lb_u32(b, w.b_len, v), cnt = lb_u32(b, w.b_len, (uint64_t)v + 1) - lt;
+            if (rank < cnt) continue;
+            const uint64_t pos = k - lt - cnt;
+            if (pos < out_len) out[pos] = v;
+        }
+        for (uint64_t k = sub; k < w.b_len; k += 8) {  // every block index is there as often as the block inserted it
+            const uint32_t v = b[k];
+            if (k != 0 && b[k - 1] == v) continue;  // once per value
+            const uint64_t cnt = lb_u32(b, w.b_len, (uint64_t)v + 1) - k;
+            const uint64_t have = lb_u32(a, w.a_len, (uint64_t)v + 1) - lb_u32(a, w.a_len, v);
+            if (have < cnt) *short_of = 1u;
+        }
+        if (sub == 0) {
+            tab[2 * w.c] = w.out_off;
+            tab[2 * w.c + 1] = out_len;
+        }
+    }
+}
+
 // apply: the nodes above the new and the written leaves, hashed again from the archive's own level arrays.  One
 // workgroup per MMR; level h's nodes are ids[off[h - 1] .. off[h]), a barrier between two levels.
 struct MsArchAncestors {
@@ -259,6 +301,11 @@ hipError_t launch_ms_arch_chunk_digests(const uint64_t* d_tab, const uint32_t* d
 hipError_t launch_ms_arch_chunks(const MsArchWritten* d_written, uint64_t n, const uint32_t* d_block_rel,
                                  const uint32_t* d_window, uint32_t* d_arena, uint64_t* d_tab, hipStream_t st) {
     return ms_launch(k_ms_arch_chunks, (size_t)(8 * n), st, d_written, n, d_block_rel, d_window, d_arena, d_tab);
+}
+
+hipError_t launch_ms_arch_unmerge(const MsArchWritten* d_rewritten, uint64_t n, const uint32_t* d_block_rel, uint32_t* d_arena,
+                                  uint64_t* d_tab, uint32_t* d_short_of, hipStream_t st) {
+    return ms_launch(k_ms_arch_unmerge, (size_t)(8 * n), st, d_rewritten, n, d_block_rel, d_arena, d_tab, d_short_of);
 }
 
 hipError_t launch_ms_arch_ancestors(const MsArchLevels m[2], const uint64_t* const d_ids[2], const uint32_t* const d_off[2],

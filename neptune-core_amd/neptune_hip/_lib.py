@@ -390,6 +390,7 @@ SIGNATURES = {
     "nhip_ms_archive_load": ([_vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64], ctypes.c_int),
     "nhip_ms_archive_accumulator": ([_vp, ctypes.POINTER(MsApplyOut)], ctypes.c_int),
     "nhip_ms_archive_apply": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut)], ctypes.c_int),
+    "nhip_ms_archive_revert": ([_vp, ctypes.POINTER(MsApplyIn), ctypes.POINTER(MsApplyOut)], ctypes.c_int),
     "nhip_ms_archive_paths": ([_vp, ctypes.c_int, _vp, _sz, _vp, _vp, _sz, ctypes.POINTER(_sz)], ctypes.c_int),
     "nhip_ms_archive_leaves": ([_vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp], ctypes.c_int),
     "nhip_ms_archive_restore": ([_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(MsUpdated)], ctypes.c_int),

@@ -748,7 +748,7 @@ def aocl_range(index_set: AbsoluteIndexSet) -> Tuple[int, int]:
 class Archive:
     """`ArchivalMutatorSet` (util_types/mutator_set/archival_mutator_set.rs) resident on the device
     (`nhip_ms_archive_*`): every node of both MMRs, every chunk and the window.  `load` uploads a whole set once and
-    builds every digest on the device; `apply` advances it across one block; `accumulator` reads the `MutatorSetAccumulator`; `aocl_paths`, `swbf_paths`
+    builds every digest on the device; `apply` advances it across one block and `revert` takes it back across one; `accumulator` reads the `MutatorSetAccumulator`; `aocl_paths`, `swbf_paths`
     and `leaves` are the archival MMRs' `prove_membership` and `get_leaf_range_inclusive`;
     `restore_membership_proofs`, `restore_dictionaries` and `restore_privacy_preserving` make fresh witnesses, in
     the form `WitnessStore.append` takes.  `initial`: a dict of initial capacities (`aocl_leafs`, `chunks`,
@@ -803,6 +803,16 @@ class Archive:
         pa = PackedApply([(msa_before, update)], None if expected is None else [expected])
         check(self.ctx.lib.nhip_ms_archive_apply(self._h, ctypes.byref(pa.cin), ctypes.byref(pa.cout)),
               "nhip_ms_archive_apply")
+        return _apply_results(pa)[0]
+
+    def revert(self, msa_before, update, expected=None):
+        """One block back (`ArchivalState::update_mutator_set`'s walk over an abandoned block): the archive stands at
+        the accumulator after `update` and is taken to `msa_before`.  `(verdict, status, bad_record, msa_after)` as
+        `apply` gives them, `msa_after` being the tip the block leads to; UPDATE_MISMATCH if that is not the archive's
+        own accumulator.  Unless the status is OK the archive is unchanged."""
+        pa = PackedApply([(msa_before, update)], None if expected is None else [expected])
+        check(self.ctx.lib.nhip_ms_archive_revert(self._h, ctypes.byref(pa.cin), ctypes.byref(pa.cout)),
+              "nhip_ms_archive_revert")
         return _apply_results(pa)[0]
 
     def accumulator(self) -> MutatorSetAccumulator:

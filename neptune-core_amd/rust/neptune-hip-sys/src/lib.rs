@@ -716,6 +716,8 @@ extern "C" {
     pub fn nhip_ms_archive_accumulator(archive: *mut nhip_ms_archive, out: *mut nhip_ms_apply_out) -> c_int;
     pub fn nhip_ms_archive_apply(archive: *mut nhip_ms_archive, block: *const nhip_ms_apply_in,
                                  block_out: *mut nhip_ms_apply_out) -> c_int;
+    pub fn nhip_ms_archive_revert(archive: *mut nhip_ms_archive, block: *const nhip_ms_apply_in,
+                                  block_out: *mut nhip_ms_apply_out) -> c_int;
     pub fn nhip_ms_archive_paths(archive: *mut nhip_ms_archive, which: c_int, leaf_index: *const u64, n: usize,
                                  path_off: *mut u64, path: *mut u64, path_cap: usize, path_digests: *mut usize) -> c_int;
     pub fn nhip_ms_archive_leaves(archive: *mut nhip_ms_archive, which: c_int, first: u64, n: u64,

@@ -12,7 +12,10 @@ best and median of --repeats:
   * restore  : nhip_ms_archive_restore of --witnesses membership proofs whose 45 indices lie around the leaf's batch
                (fill call).  gather_GBps is the bytes k_ms_arch_gather reads plus writes over its event time;
   * apply    : nhip_ms_archive_apply of a block of 64 addition records (eight window slides) on the fresh archive,
-               whose arrays all have to grow for it (the wall time includes packing the block in Python).
+               whose arrays all have to grow for it (the wall time includes packing the block in Python);
+  * revert   : nhip_ms_archive_revert of that block, back to the loaded set (packing included, as apply's);
+  * reload   : the only other way back: destroy, create and load of the whole set before.  It needs every leaf, chunk
+               word and the window of the earlier set on the host; the revert needs the block alone.
 A sample of the restored AOCL paths is checked with nhip_mmr_verify_batch against the archive's own accumulator.
 One JSON line per leaf count.
 
@@ -115,6 +118,20 @@ def main():
                 timed("restore", lambda: lib.nhip_ms_archive_restore(archive._h, mn.ctypes.data, dist.ctypes.data,
                                                                      leaf.ctypes.data, W, ctypes.byref(cout)))
                 timed("apply", lambda: (archive.apply(acc[0], block), L.NHIP_OK)[1])
+                back = [None]
+
+                def revert():
+                    back[0] = archive.revert(acc[0], block)
+                    return L.NHIP_OK
+                timed("revert", revert)
+                assert back[0][:2] == (True, MS.OK) and archive.counts()[:3] == (N, B, WINDOW), back[0][:3]
+
+                def reload():
+                    nonlocal archive
+                    archive.close()
+                    archive = MS.Archive(ctx)
+                    return archive.load_raw(leaves, rel_off, rel, window)
+                timed("reload", reload)
                 if rep == 0:
                     stats.clear()
             assert not o["status"].any() and (o["aocl_path_off"] == poff).all() and (o["aocl_path"][:A] == ppath[:A]).all()
