@@ -952,7 +952,8 @@ int nhip_ms_revert_batch(nhip_ctx *ctx, const nhip_ms_apply_in *block, nhip_ms_a
  * A store owns the witnesses of nhip_ms_update_batch (same description: nhip_ms_update_in) in device memory of
  * its own and brings all of them across one block per nhip_ms_store_update: §6g for one job, its witness side
  * bound to the store.  Only the block, the plan's integer arrays, block_out and one status byte per witness cross
- * to or from the host; no path digest and no chunk word of a witness does after nhip_ms_store_append.  The host
+ * to or from the host; no path digest and no chunk word of a witness does after nhip_ms_store_append, or at all,
+ * through nhip_ms_store_append_restored.  The host
  * keeps a mirror of the integers alone (index sets, leaf indices, the four offset arrays, the keys).
  * Witnesses are numbered 0 .. W-1 in insertion order; the positions are stable until nhip_ms_store_retain.
  * A store belongs to one nhip_ctx (which must outlive it) and to one tip; calls on it are serialized by the
@@ -1115,6 +1116,33 @@ int nhip_ms_archive_restore(nhip_ms_archive *archive, const uint64_t *minimum, c
 int nhip_ms_archive_restore_plan(uint64_t aocl_leafs, const uint64_t *chunk_len, uint64_t n_chunks,
                                  const uint64_t *minimum, const uint32_t *distances, const uint64_t *aocl_leaf_index,
                                  size_t n, nhip_ms_updated *out);
+/* nhip_ms_archive_restore_plan decided on the device, from the archive's own chunk table: the same outputs (status, the
+ * four offset arrays, the keys, the totals; aocl_path, path and rel are left alone) with the two-call sizing of
+ * nhip_ms_archive_restore, equal integer for integer to the host plan.  Only the index sets and the leaf indices go
+ * up and only these integers come back; totals past the plan's limits are NHIP_ERR_OOM.  The kernels work on
+ * NHIP_MS_RESTORE_WAVES witnesses per workgroup and scan in tiles of NHIP_MS_RESTORE_SCAN_WIDTH items, whose sums
+ * NHIP_MS_RESTORE_CARRY_LANES lanes carry across the grid. */
+#define NHIP_MS_RESTORE_WAVES 4
+#define NHIP_MS_RESTORE_SCAN_WIDTH 256
+#define NHIP_MS_RESTORE_CARRY_LANES 64
+int nhip_ms_archive_restore_shape(nhip_ms_archive *archive, const uint64_t *minimum, const uint32_t *distances,
+                                  const uint64_t *aocl_leaf_index, size_t n, nhip_ms_updated *out);
+/* nhip_ms_archive_restore followed by nhip_ms_store_append of its output, device to device: afterwards the store
+ * holds exactly what those two calls leave in it (device arrays, mirror, every later read, update, revert, retain
+ * and check), and no path digest and no chunk word has crossed to the host.  The restore's shape is decided on the
+ * device (nhip_ms_archive_restore_shape), the gather writes behind the store's totals, and only integers come back:
+ * the statuses, the totals, the offset tails and the keys, which the store's mirror holds anyway.
+ *   aocl_leaf  n x 5 words, as nhip_ms_update_in carries it, stored as given; NULL: a witness with a leaf index gets
+ *              the archive's own level-0 digest at that index, one without gets zeros.
+ *   status     n bytes or NULL: the restore's per-witness status.
+ * All or nothing: unless every status is NHIP_MS_OK the store is unchanged and the return is NHIP_OK with the
+ * statuses written; the caller filters and calls again.  n == 0 is NHIP_OK and changes nothing.  NHIP_ERR_ARG before
+ * anything is touched: a NULL store or archive, an archive of another nhip_ctx than the store's, NULL inputs with
+ * n > 0.  A poisoned archive is NHIP_ERR_HIP.  NHIP_ERR_OOM and NHIP_ERR_HIP leave the store as it was (every growth
+ * precedes the first write, the mirror is committed behind a clean drain); the archive is only read. */
+int nhip_ms_store_append_restored(nhip_ms_store *store, nhip_ms_archive *archive, const uint64_t *minimum,
+                                  const uint32_t *distances, const uint64_t *aocl_leaf_index,
+                                  const uint64_t *aocl_leaf, size_t n, uint8_t *status);
 
 /* ---- a block file's mutator-set and transaction rules ---------------------------
  * Block::validate rules 2.a-2.l (protocol/consensus/block/mod.rs:811-891) for every (parent, child) pair of

@@ -77,7 +77,9 @@ extern "C" {
 // 3100: witnesses back across a block (nhip_ms_revert_plan, nhip_ms_revert_batch, nhip_ms_store_revert)
 // 3200: the archival mutator set resident on the device (nhip_ms_archive_*)
 // 3300: the archival mutator set back across a block (nhip_ms_archive_revert)
-int nhip_abi_version(void) { return 3300; }
+// 3400: restored witnesses straight into a store (nhip_ms_archive_restore_shape, nhip_ms_store_append_restored;
+// DESIGN.md §6k)
+int nhip_abi_version(void) { return 3400; }
 
 int nhip_set_fs_form(int form) { return nhip::set_fs_form(form) == 0 ? NHIP_OK : NHIP_ERR_ARG; }
 int nhip_set_climb_from_ops(int64_t ops) { return nhip::set_climb_from_ops(ops) == 0 ? NHIP_OK : NHIP_ERR_ARG; }

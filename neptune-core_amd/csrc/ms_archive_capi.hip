@@ -9,6 +9,7 @@
 #include "ms_parts.hpp"
 #include "ms_archive.hpp"
 #include "ms_archive_device.hpp"
+#include "ms_restore_device.hpp"
 
 namespace {
 
@@ -708,4 +709,57 @@ int nhip_ms_archive_restore(nhip_ms_archive* a, const uint64_t* minimum, const u
     }
 }
 
+// nhip_ms_archive_restore_plan on the device (ms_restore_kernels.hip): the inputs go up, the shape kernels run into
+// stage scratch, the totals, the statuses and the per-witness offsets come back with one drain, the limits are decided
+// from the totals, and a second, smaller read fetches the per-entry arrays, whose length is only known then.
+int nhip_ms_archive_restore_shape(nhip_ms_archive* a, const uint64_t* minimum, const uint32_t* distances,
+                                  const uint64_t* aocl_leaf_index, size_t n, nhip_ms_updated* out) {
+    if (!a || !out) return NHIP_ERR_ARG;
+    if (n && (!minimum || !distances || !aocl_leaf_index)) return NHIP_ERR_ARG;
+    if (n > 0xFFFFFFFFull) return NHIP_ERR_OOM;
+    nhip_ctx* c = a->c;
+    try {
+        Stage st(c);
+        if (a->poisoned) return NHIP_ERR_HIP;
+        nhip::MsUpdatePlan plan;  // the shape as ms_updated_check and ms_updated_write read it
+        plan.wit_job.assign(n, 0);
+        plan.aocl_path_off.assign(n + 1, 0);
+        plan.entry_off.assign(n + 1, 0);
+        plan.path_off.assign(1, 0);
+        plan.rel_off.assign(1, 0);
+        std::vector<uint8_t> status(n);
+        nhip::RestoreShapePart shape(nhip::ms_archive_view(a), n);
+        if (n) {
+            shape.declare(st, minimum, distances, aocl_leaf_index);
+            if (st.commit()) return st.finish();
+            shape.enqueue(st, c, status.data());
+            st.out(plan.aocl_path_off.data(), shape.d.aocl_path_off, n + 1);
+            st.out(plan.entry_off.data(), shape.d.entry_off, n + 1);
+            int rc = st.finish();
+            if (rc == NHIP_OK) rc = shape.limits();
+            if (rc != NHIP_OK) return rc;
+            const size_t E = (size_t)shape.totals[1];
+            plan.chunk_index.resize(E);
+            plan.path_off.resize(E + 1);
+            plan.rel_off.resize(E + 1);
+            st.out(plan.chunk_index.data(), shape.d.chunk_index, E);
+            st.out(plan.path_off.data(), shape.d.path_off, E + 1);
+            st.out(plan.rel_off.data(), shape.d.rel_off, E + 1);
+            if ((rc = st.finish()) != NHIP_OK) return rc;
+        }
+        if (const int rc = nhip::ms_updated_check(plan, false, out)) return rc;
+        nhip::ms_updated_write(plan, true, out);
+        if (out->status) std::copy(status.begin(), status.end(), out->status);
+        return NHIP_OK;
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
 }  // extern "C"
+
+nhip::MsArchView nhip::ms_archive_view(const nhip_ms_archive* a) {
+    return MsArchView{a->poisoned, a->levels(0), a->levels(1), a->tab.p, a->arena.p};
+}
+
+nhip_ctx* nhip::ms_archive_ctx(const nhip_ms_archive* a) { return a->c; }

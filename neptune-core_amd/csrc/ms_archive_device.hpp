@@ -33,6 +33,9 @@ struct MsArchRelPool {
     uint64_t owners, units;
     const uint32_t* first;
     uint32_t* dst;
+    // 0 or 1: the pool's word w is element w + skew of dst, which is 8-byte aligned either way (a pool that begins at
+    // an odd word of a larger array); units and `first` then count elements of dst, the first of which is nobody's
+    uint64_t skew;
 };
 struct MsArchGatherDev {
     MsArchPathPool path[2];

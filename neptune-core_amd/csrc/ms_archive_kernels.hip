@@ -28,11 +28,16 @@
 //                            digest t of leaf i's path is arithmetic: node (t, (i >> t) ^ 1).  Chunk words are u32 and
 //                            a range may begin on a 4-byte boundary: a lane takes an aligned pair of destination
 //                            words, finds each word's source on its own and stores 8 bytes; only the pool's last word
-//                            can be a 4-byte store.
+//                            can be a 4-byte store (or its first, where the pool begins on an odd word of a store's:
+//                            MsArchRelPool::skew).
+//  k_ms_arch_gather_own    : the hand-over of restored witnesses to a store.  The same gather for offsets made on the
+//                            device (ms_restore_kernels.hip): no host map names a unit's owners, so each unit finds
+//                            those of its first and last word by two searches of the whole offset array.
 // Every lane writes inside the ranges the host planned only: a level's n >> h nodes, the destination totals.
 #include "ms_archive.hpp"
 #include "ms_archive_device.hpp"
 #include "ms_device.hpp"
+#include "ms_restore_device.hpp"
 
 namespace nhip {
 
@@ -71,11 +76,10 @@ __device__ __forceinline__ uint64_t owner(const uint64_t* __restrict__ off, uint
     return a - 1;
 }
 
-__device__ __forceinline__ void gather_paths(const MsArchPathPool& p, uint64_t u) {
+// sa, hi: the unit's owners lie in [sa, hi)
+__device__ __forceinline__ void gather_paths(const MsArchPathPool& p, uint64_t u, uint64_t sa, uint64_t hi) {
     const uint64_t total = 5 * p.dst_off[p.owners];
     const uint64_t g0 = u * UNIT, g1 = g0 + UNIT < total ? g0 + UNIT : total;
-    // the last word's owner is at most the next unit's first (owners - 1 behind the last unit)
-    const uint64_t sa = p.first[u], hi = (uint64_t)p.first[u + 1] + 1;
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) {
         const uint64_t g = g0 + k * ARCH_THREADS + threadIdx.x;
@@ -92,20 +96,36 @@ __device__ __forceinline__ uint32_t rel_word(const MsArchRelPool& p, uint64_t s,
     return p.arena[p.tab[2 * (p.key ? p.key[s] : s)] + (w - p.dst_off[s])];  // key null: chunk s (compaction)
 }
 
-__device__ __forceinline__ void gather_rel(const MsArchRelPool& p, uint64_t u) {
-    const uint64_t total = p.dst_off[p.owners];
-    const uint64_t w0 = 2 * u * UNIT, w1 = w0 + 2 * UNIT < total ? w0 + 2 * UNIT : total;
-    const uint64_t sa = p.first[u], hi = (uint64_t)p.first[u + 1] + 1;
-    for (uint64_t w = w0 + 2 * (uint64_t)threadIdx.x; w < w1; w += 2 * ARCH_THREADS) {
-        const uint64_t s = owner(p.dst_off, 1, sa, hi, w);
-        const uint32_t v0 = rel_word(p, s, w);
-        if (w + 1 < w1) {
-            const uint64_t s1 = w + 1 < p.dst_off[s + 1] ? s : owner(p.dst_off, 1, sa, hi, w + 1);
-            *reinterpret_cast<uint2*>(p.dst + w) = make_uint2(v0, rel_word(p, s1, w + 1));  // w even, dst 256-byte aligned
-        } else {
-            p.dst[w] = v0;
+// A unit's pairs are aligned in the destination array: word w of the pool is element w + skew of p.dst, which is
+// 8-byte aligned, and a unit takes the elements [2 u UNIT, 2 (u + 1) UNIT); the elements below skew belong to nobody.
+__device__ __forceinline__ void gather_rel(const MsArchRelPool& p, uint64_t u, uint64_t sa, uint64_t hi) {
+    const uint64_t skew = p.skew, end = p.dst_off[p.owners] + skew;
+    const uint64_t x0 = 2 * u * UNIT, x1 = x0 + 2 * UNIT < end ? x0 + 2 * UNIT : end;
+    for (uint64_t x = x0 + 2 * (uint64_t)threadIdx.x; x < x1; x += 2 * ARCH_THREADS) {
+        const bool low = x >= skew, high = x + 1 < x1;  // skew <= 1: the high element is a word whenever it is in range
+        uint64_t s = 0;
+        uint32_t v0 = 0, v1 = 0;
+        if (low) {
+            s = owner(p.dst_off, 1, sa, hi, x - skew);
+            v0 = rel_word(p, s, x - skew);
         }
+        if (high) {
+            const uint64_t w = x + 1 - skew;
+            const uint64_t s1 = low && w < p.dst_off[s + 1] ? s : owner(p.dst_off, 1, sa, hi, w);
+            v1 = rel_word(p, s1, w);
+        }
+        if (low && high) *reinterpret_cast<uint2*>(p.dst + x) = make_uint2(v0, v1);  // x even, dst 8-byte aligned
+        else if (low) p.dst[x] = v0;
+        else if (high) p.dst[x + 1] = v1;
     }
+}
+
+// the unit's owners when no host map names them: those of its first and of its last word, by two searches of the
+// whole offset array, the same in every lane
+__device__ __forceinline__ void own_range(const uint64_t* __restrict__ off, uint64_t owners, uint64_t scale, uint64_t g0,
+                                          uint64_t g_last, uint64_t* sa, uint64_t* hi) {
+    *sa = owner(off, scale, 0, owners, g0);
+    *hi = owner(off, scale, *sa, owners, g_last) + 1;
 }
 
 }  // namespace
@@ -276,9 +296,32 @@ __global__ void __launch_bounds__(ARCH_THREADS) k_ms_arch_ancestors(MsArchAncest
 __global__ void __launch_bounds__(ARCH_THREADS) k_ms_arch_gather(MsArchGatherDev g) {
     const uint64_t e0 = g.path[0].units, e1 = e0 + g.path[1].units, e2 = e1 + g.rel.units;
     for (uint64_t u = blockIdx.x; u < e2; u += gridDim.x) {
-        if (u < e0) gather_paths(g.path[0], u);
-        else if (u < e1) gather_paths(g.path[1], u - e0);
-        else gather_rel(g.rel, u - e1);
+        // the last word's owner is at most the next unit's first (owners - 1 behind the last unit)
+        if (u < e0) gather_paths(g.path[0], u, g.path[0].first[u], (uint64_t)g.path[0].first[u + 1] + 1);
+        else if (u < e1) gather_paths(g.path[1], u - e0, g.path[1].first[u - e0], (uint64_t)g.path[1].first[u - e0 + 1] + 1);
+        else gather_rel(g.rel, u - e1, g.rel.first[u - e1], (uint64_t)g.rel.first[u - e1 + 1] + 1);
+    }
+}
+
+// The same gather for pools whose offsets were made on the device (ms_restore_kernels.hip), where no host map can
+// name a unit's owners: every unit finds them itself.
+__global__ void __launch_bounds__(ARCH_THREADS) k_ms_arch_gather_own(MsArchGatherDev g) {
+    const uint64_t e0 = g.path[0].units, e1 = e0 + g.path[1].units, e2 = e1 + g.rel.units;
+    for (uint64_t u = blockIdx.x; u < e2; u += gridDim.x) {
+        uint64_t sa, hi;
+        if (u < e1) {
+            const MsArchPathPool& p = u < e0 ? g.path[0] : g.path[1];
+            const uint64_t v = u < e0 ? u : u - e0, total = 5 * p.dst_off[p.owners];
+            const uint64_t g0 = v * UNIT, g1 = g0 + UNIT < total ? g0 + UNIT : total;  // g0 < total: the unit exists
+            own_range(p.dst_off, p.owners, 5, g0, g1 - 1, &sa, &hi);
+            gather_paths(p, v, sa, hi);
+        } else {
+            const MsArchRelPool& p = g.rel;
+            const uint64_t v = u - e1, skew = p.skew, end = p.dst_off[p.owners] + skew;
+            const uint64_t x0 = 2 * v * UNIT, x1 = x0 + 2 * UNIT < end ? x0 + 2 * UNIT : end;
+            own_range(p.dst_off, p.owners, 1, (x0 > skew ? x0 : skew) - skew, x1 - 1 - skew, &sa, &hi);  // x1 > skew: units from the words
+            gather_rel(p, v, sa, hi);
+        }
     }
 }
 
@@ -326,6 +369,13 @@ hipError_t launch_ms_arch_gather(const MsArchGatherDev& g, hipStream_t st) {
     const uint64_t units = g.path[0].units + g.path[1].units + g.rel.units;
     if (units == 0) return hipSuccess;
     hipLaunchKernelGGL(k_ms_arch_gather, dim3((unsigned)(units > 8192 ? 8192 : units)), dim3(ARCH_THREADS), 0, st, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_ms_arch_gather_own(const MsArchGatherDev& g, hipStream_t st) {
+    const uint64_t units = g.path[0].units + g.path[1].units + g.rel.units;
+    if (units == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ms_arch_gather_own, dim3((unsigned)(units > 8192 ? 8192 : units)), dim3(ARCH_THREADS), 0, st, g);
     return hipGetLastError();
 }
 

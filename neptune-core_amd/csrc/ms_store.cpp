@@ -71,6 +71,48 @@ void ms_store_append_commit(MsStoreMirror& m, const nhip_ms_update_in* wit, size
     m.sticky.insert(m.sticky.end(), n, (uint8_t)NHIP_MS_OK);
 }
 
+int ms_store_restored_ok(const MsStoreMirror& m, size_t n, const uint64_t add[4]) {
+    if (n >= (size_t)UINT32_MAX) return NHIP_ERR_ARG;
+    const MsUpdateCounts have = m.counts();
+    const uint64_t lim = MS_STORE_LIMIT;  // no sum wraps: each addend is compared alone first
+    if (add[0] > lim || add[1] > lim || add[2] > lim || add[3] > lim) return NHIP_ERR_OOM;
+    if (have.witnesses + n >= (uint64_t)UINT32_MAX || have.chunks.entries + add[1] >= (uint64_t)UINT32_MAX ||
+        have.witnesses + n > lim || have.aocl_digests + add[0] > lim || have.chunks.path_digests + add[2] > lim ||
+        have.chunks.rel_words + add[3] > lim)
+        return NHIP_ERR_OOM;
+    return NHIP_OK;
+}
+
+void ms_store_append_restored_commit(MsStoreMirror& m, const MsStoreRestored& r) {
+    const size_t n = r.n;
+    if (n == 0) return;
+    const size_t W = m.witnesses(), E = m.entries(), ne = (size_t)r.entry_off[n];
+    const MsUpdateCounts have = m.counts();
+    m.minimum.reserve(2 * (W + n));
+    m.distances.reserve(45 * (W + n));
+    m.leaf_index.reserve(W + n);
+    m.aocl_path_off.reserve(W + n + 1);
+    m.entry_off.reserve(W + n + 1);
+    m.key.reserve(E + ne);
+    m.path_off.reserve(E + ne + 1);
+    m.rel_off.reserve(E + ne + 1);
+    m.sticky.reserve(W + n);
+    // nothing below allocates
+    m.minimum.insert(m.minimum.end(), r.minimum, r.minimum + 2 * n);
+    m.distances.insert(m.distances.end(), r.distances, r.distances + 45 * n);
+    m.leaf_index.insert(m.leaf_index.end(), r.leaf_index, r.leaf_index + n);
+    for (size_t i = 0; i < n; ++i) {
+        m.aocl_path_off.push_back(have.aocl_digests + r.aocl_path_off[i + 1]);
+        m.entry_off.push_back(have.chunks.entries + r.entry_off[i + 1]);
+    }
+    for (size_t e = 0; e < ne; ++e) {
+        m.key.push_back(r.chunk_index[e]);
+        m.path_off.push_back(have.chunks.path_digests + r.path_off[e + 1]);
+        m.rel_off.push_back(have.chunks.rel_words + r.rel_off[e + 1]);
+    }
+    m.sticky.insert(m.sticky.end(), n, (uint8_t)NHIP_MS_OK);
+}
+
 int ms_store_select(const MsStoreMirror& m, const uint64_t* sel, size_t n, MsStoreSelect* s) {
     *s = MsStoreSelect{};
     const size_t W = m.witnesses();

@@ -62,6 +62,23 @@ int ms_store_append_plan(const MsStoreMirror& m, const nhip_ms_update_in* wit, s
 // after a plan that returned NHIP_OK; throws std::bad_alloc before it changes anything
 void ms_store_append_commit(MsStoreMirror& m, const nhip_ms_update_in* wit, size_t n, const MsStoreAppend& a);
 
+// ---- append, from a restore whose shape was decided on the device (nhip_ms_store_append_restored):
+// the plan's integers as they came back, all four offset arrays beginning at 0.  No path and no chunk word exists on
+// the host, so there is no nhip_ms_update_in to read.
+struct MsStoreRestored {
+    size_t n = 0;                                                    // witnesses, every one NHIP_MS_OK
+    const uint64_t *minimum = nullptr, *leaf_index = nullptr;        // n x 2, n
+    const uint32_t* distances = nullptr;                             // n x 45
+    const uint64_t *aocl_path_off = nullptr, *entry_off = nullptr;   // n + 1
+    const uint64_t* chunk_index = nullptr;                           // entry_off[n]
+    const uint64_t *path_off = nullptr, *rel_off = nullptr;          // entry_off[n] + 1
+};
+// ms_store_append_plan's limits for totals (AOCL digests, entries, path digests, chunk words) that n witnesses add:
+// NHIP_ERR_ARG for n >= 2^32 - 1, NHIP_ERR_OOM past MS_STORE_LIMIT or 2^32 - 1 witnesses or entries
+int ms_store_restored_ok(const MsStoreMirror& m, size_t n, const uint64_t add[4]);
+// what ms_store_append_commit leaves for the same integers; throws std::bad_alloc before it changes anything
+void ms_store_append_restored_commit(MsStoreMirror& m, const MsStoreRestored& r);
+
 // ---- select: the witnesses sel[0 .. n) in that order, repeats allowed (read), or the kept ones (retain)
 // Pools: 0 AOCL path digests, 1 entries (keys), 2 dictionary path digests, 3 chunk words (u32).
 struct MsStoreSelect {

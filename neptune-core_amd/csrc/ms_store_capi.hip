@@ -10,6 +10,7 @@
 // and every shape decision); the block and witness parts are ms_parts.hpp's, shared with nhip_ms_update_batch and
 // nhip_ms_revert_batch.
 #include "ms_parts.hpp"
+#include "ms_restore_device.hpp"
 #include "ms_store.hpp"
 
 namespace {
@@ -316,6 +317,104 @@ int nhip_ms_store_append(nhip_ms_store* s, const nhip_ms_update_in* wit, size_t 
         st.up(F.leaf.p + 5 * W0, wit->aocl_leaf, 5 * n);
         if ((rc = st.finish()) != NHIP_OK) return rc;
         nhip::ms_store_append_commit(s->m, wit, n, a);
+        return NHIP_OK;
+    } catch (const std::bad_alloc&) {
+        return NHIP_ERR_OOM;
+    }
+}
+
+// nhip_ms_archive_restore and nhip_ms_store_append in one, device to device ("The hand-over"): the
+// shape kernels into stage scratch, one drain for the totals and the statuses, all or nothing and the limits, every
+// growth, then the gather out of the archive straight behind the store's totals, the offsets rebased into the shape
+// arrays, the fixed arrays, and the integers the mirror needs back to the host.
+int nhip_ms_store_append_restored(nhip_ms_store* s, nhip_ms_archive* archive, const uint64_t* minimum, const uint32_t* distances,
+                                  const uint64_t* aocl_leaf_index, const uint64_t* aocl_leaf, size_t n, uint8_t* status) {
+    if (!s || !archive || nhip::ms_archive_ctx(archive) != s->c) return NHIP_ERR_ARG;
+    nhip_ctx* c = s->c;
+    if (n && (!minimum || !distances || !aocl_leaf_index)) return NHIP_ERR_ARG;
+    if (n >= (size_t)UINT32_MAX) return NHIP_ERR_ARG;  // as nhip_ms_store_append
+    try {
+        Stage st(c);  // one context: its lock covers the archive too
+        const nhip::MsArchView av = nhip::ms_archive_view(archive);
+        if (av.poisoned) return NHIP_ERR_HIP;
+        if (n == 0) return NHIP_OK;
+        std::vector<uint8_t> wstatus(n);
+        nhip::RestoreShapePart shape(av, n);
+        shape.declare(st, minimum, distances, aocl_leaf_index);
+        if (st.commit()) return st.finish();
+        shape.enqueue(st, c, wstatus.data());
+        int rc = st.finish();
+        if (rc != NHIP_OK) return rc;
+        if (status) std::copy(wstatus.begin(), wstatus.end(), status);
+        if (std::any_of(wstatus.begin(), wstatus.end(), [](uint8_t x) { return x != NHIP_MS_OK; })) return NHIP_OK;
+        if ((rc = shape.limits()) != NHIP_OK) return rc;
+        const uint64_t* add = shape.totals;
+        if ((rc = nhip::ms_store_restored_ok(s->m, n, add)) != NHIP_OK) return rc;
+        uint64_t have[4], need[4];
+        const nhip::MsUpdateCounts hc = s->m.counts();
+        totals_of(hc, have);
+        for (int p = 0; p < 4; ++p) need[p] = have[p] + add[p];
+        const size_t W0 = (size_t)hc.witnesses, E0 = (size_t)have[1], ne = (size_t)add[1];
+        // host memory first: what the mirror's commit reads
+        std::vector<uint64_t> aocl_path_off(n + 1), entry_off(n + 1), key(ne), path_off(ne + 1), rel_off(ne + 1);
+        Pools& P = s->pools[s->pc];
+        Shape& H = s->shape[s->sc];
+        Fixed& F = s->fixed[s->fc];
+        rc = P.ensure(need, have, c->stream);
+        if (!rc) rc = H.ensure(W0 + n, E0 + ne, W0, E0, true, c->stream);
+        if (!rc) rc = F.ensure(W0 + n, W0, c->stream);
+        if (rc) return rc;
+        // ---- from here on only bytes behind the mirror's totals are written
+        const uint64_t skew = have[3] & 1;  // the chunk words' pool may begin on an odd word: the gather stores aligned pairs
+        nhip::MsArchGatherDev g{};
+        nhip::MsArchPathPool& pa = g.path[0];
+        nhip::MsArchPathPool& ps = g.path[1];
+        nhip::MsArchRelPool& pr = g.rel;
+        const uint64_t unit = nhip::MS_ARCHIVE_GATHER_UNIT;
+        pa.mmr = av.aocl, pa.leaf = shape.d.leaf_index, pa.dst_off = shape.d.aocl_path_off, pa.owners = n;
+        pa.units = (5 * add[0] + unit - 1) / unit, pa.dst = P.aocl.p + 5 * (size_t)have[0];
+        ps.mmr = av.swbf, ps.leaf = shape.d.chunk_index, ps.dst_off = shape.d.path_off, ps.owners = ne;
+        ps.units = (5 * add[2] + unit - 1) / unit, ps.dst = P.path.p + 5 * (size_t)have[2];
+        pr.tab = av.tab, pr.arena = av.arena, pr.key = shape.d.chunk_index, pr.dst_off = shape.d.rel_off, pr.owners = ne;
+        pr.units = add[3] ? (add[3] + skew + 2 * unit - 1) / (2 * unit) : 0;
+        pr.dst = P.rel.p + (size_t)(have[3] - skew), pr.skew = skew;
+        st.launch([&] { return nhip::launch_ms_arch_gather_own(g, c->stream); });
+        nhip::MsRestoreHandDev hd{};
+        hd.s = shape.d;
+        hd.entries = ne;
+        for (int p = 0; p < 4; ++p) hd.base[p] = have[p];
+        hd.w0 = W0;
+        hd.aocl_path_off = H.aocl_path_off.p, hd.entry_off = H.entry_off.p, hd.path_off = H.path_off.p, hd.rel_off = H.rel_off.p;
+        hd.key = P.key.p;
+        hd.aocl_nodes = av.aocl.nodes;
+        hd.leaf = aocl_leaf ? nullptr : F.leaf.p;
+        static const uint64_t zero = 0;
+        if (E0 == 0 && ne == 0) {  // no entry lane writes the first offsets
+            st.up(H.path_off.p, &zero, 1);
+            st.up(H.rel_off.p, &zero, 1);
+        }
+        st.launch([&] { return nhip::launch_ms_restore_hand(hd, c->stream); });
+        st.step([&] { return nhip::hip_fail(hipMemsetAsync(H.sticky.p + W0, NHIP_MS_OK, n, c->stream)); });
+        auto d2d = [&](void* dst, const void* src, size_t bytes) {
+            st.step([&] { return nhip::hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream)); });
+        };
+        d2d(F.minimum.p + 2 * W0, shape.d.minimum, 16 * n);
+        d2d(F.distances.p + 45 * W0, shape.d.distances, 4 * 45 * n);
+        d2d(F.leaf_index.p + W0, shape.d.leaf_index, 8 * n);
+        if (aocl_leaf) st.up(F.leaf.p + 5 * W0, aocl_leaf, 5 * n);
+        // the integers the mirror needs: the offsets (from 0, the commit rebases them) and the keys
+        st.out(aocl_path_off.data(), shape.d.aocl_path_off, n + 1);
+        st.out(entry_off.data(), shape.d.entry_off, n + 1);
+        st.out(key.data(), shape.d.chunk_index, ne);
+        st.out(path_off.data(), shape.d.path_off, ne + 1);
+        st.out(rel_off.data(), shape.d.rel_off, ne + 1);
+        if ((rc = st.finish()) != NHIP_OK) return rc;
+        nhip::MsStoreRestored r;
+        r.n = n;
+        r.minimum = minimum, r.leaf_index = aocl_leaf_index, r.distances = distances;
+        r.aocl_path_off = aocl_path_off.data(), r.entry_off = entry_off.data(), r.chunk_index = key.data();
+        r.path_off = path_off.data(), r.rel_off = rel_off.data();
+        nhip::ms_store_append_restored_commit(s->m, r);
         return NHIP_OK;
     } catch (const std::bad_alloc&) {
         return NHIP_ERR_OOM;

@@ -199,6 +199,11 @@ class MsArchiveCaps(ctypes.Structure):
 
 
 MS_ARCHIVE_TAIL_NODES = 256  # NHIP_MS_ARCHIVE_TAIL_NODES: load gives a level a launch of its own while the level below has more nodes
+# the restore shape kernels' geometry (nhip_ms_archive_restore_shape): witnesses per workgroup, items per scan tile,
+# lanes that carry the tile sums across the grid
+MS_RESTORE_WAVES = 4  # NHIP_MS_RESTORE_WAVES
+MS_RESTORE_SCAN_WIDTH = 256  # NHIP_MS_RESTORE_SCAN_WIDTH
+MS_RESTORE_CARRY_LANES = 64  # NHIP_MS_RESTORE_CARRY_LANES
 
 
 class BlkMsParams(ctypes.Structure):
@@ -396,6 +401,8 @@ SIGNATURES = {
     "nhip_ms_archive_restore": ([_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(MsUpdated)], ctypes.c_int),
     "nhip_ms_archive_restore_plan": ([ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp, _vp, _sz,
                                       ctypes.POINTER(MsUpdated)], ctypes.c_int),
+    "nhip_ms_archive_restore_shape": ([_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(MsUpdated)], ctypes.c_int),
+    "nhip_ms_store_append_restored": ([_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp], ctypes.c_int),
     "nhip_blk_ms_params_default": ([ctypes.POINTER(BlkMsParams)], None),
     "nhip_blk_ms_walk": ([_vp, _sz, ctypes.c_uint32, _vp, _sz, ctypes.POINTER(BlkMsParts)], ctypes.c_int),
     "nhip_blk_guesser_fee_records": ([_vp, _vp, _sz, ctypes.POINTER(BlkMsParams), _vp, _sz, _vp, _vp, _vp, _vp],

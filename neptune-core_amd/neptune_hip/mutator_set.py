@@ -650,6 +650,58 @@ class WitnessStore:
         check(self.ctx.lib.nhip_ms_store_append(self._h, ctypes.byref(pw.win), pw.n), "nhip_ms_store_append")
         self._fixed += [(w.absolute_indices, w.aocl_leaf_index, w.aocl_leaf) for w in pw.witnesses]
 
+    def append_restored(self, archive, index_sets, aocl_leaf_indices, aocl_leaves=None):
+        """`archive.restore_raw` + `append` in one call, device to device (`nhip_ms_store_append_restored`): the
+        restore's shape is decided on the device, the gather writes into the store's own pools, and no path digest
+        and no chunk word crosses to the host.  Returns the restore's status per witness.  All or nothing: unless
+        every status is OK the store is unchanged; filter and call again.  `aocl_leaves`: the callers' commitments
+        (anything where the leaf index is None), or None for the archive's own leaves at the leaf indices."""
+        n = len(index_sets)
+        if n == 0:
+            return []
+
+        class _S:  # _index_arrays reads `.absolute_indices`
+            def __init__(self, s):
+                self.absolute_indices = s
+        sets = list(index_sets)
+        mn, dist = _index_arrays([_S(s) for s in sets])
+        leafs = [None if l is None else int(l) for l in aocl_leaf_indices]
+        li = np.asarray([2 ** 64 - 1 if l is None else l for l in leafs], dtype=np.uint64)
+        leaf = None
+        if aocl_leaves is not None:
+            leaf = np.zeros((n, 5), dtype=np.uint64)
+            for i, l in enumerate(leafs):
+                if l is not None:
+                    leaf[i] = np.asarray([int(x) for x in aocl_leaves[i]], dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint8)
+        check(self.ctx.lib.nhip_ms_store_append_restored(self._h, archive._h, _ptr(mn), _ptr(dist), _ptr(li),
+                                                         None if leaf is None else _ptr(leaf), n, _ptr(status)),
+              "nhip_ms_store_append_restored")
+        out = [int(x) for x in status]
+        if any(st != OK for st in out):
+            return out
+        for i, l in enumerate(leafs):  # what `read` hands back beside the device's arrays
+            if l is None:
+                given = ()
+            elif leaf is not None:
+                given = tuple(int(x) for x in leaf[i])
+            else:
+                given = tuple(int(x) for x in archive.leaves(0, l, 1)[0])
+            self._fixed.append((sets[i], l, given))
+        return out
+
+    def append_restored_membership_proofs(self, archive, items, sender_randomness, receiver_preimages,
+                                          aocl_leaf_indices, aocl_leaves=None):
+        """`append_restored` for items, as `Archive.restore_membership_proofs` takes them: the index sets are computed
+        on the device (`nhip_absolute_index_sets`)."""
+        n = len(aocl_leaf_indices)
+        if n == 0:
+            return []
+        it, sr, rp = _digests(items, n), _digests(sender_randomness, n), _digests(receiver_preimages, n)
+        leafs = [int(l) for l in aocl_leaf_indices]
+        sets = AbsoluteIndexSet.compute_batch(self.ctx, it, sr, rp, leafs)
+        return self.append_restored(archive, sets, leafs, aocl_leaves)
+
     def update(self, msa_before, update, expected=None):
         """One block: `((verdict, status, bad_record, msa_after), [status of every witness])`.  Unless the block's
         status is OK the store is unchanged and every witness status is JOB_REJECTED."""
@@ -866,6 +918,13 @@ class Archive:
         """Both calls of the two-call pattern of `nhip_ms_archive_restore`: `(count-pass totals, output arrays)`."""
         return _restore_two_calls(lambda mn, dist, li, n, cout: self.ctx.lib.nhip_ms_archive_restore(
             self._h, _ptr(mn), _ptr(dist), _ptr(li), n, cout), "nhip_ms_archive_restore", index_sets, aocl_leaf_indices)
+
+    def restore_shape(self, index_sets, aocl_leaf_indices):
+        """`restore_plan` decided on the device from the archive's own chunk table (`nhip_ms_archive_restore_shape`):
+        `(totals, output arrays)` in the same form, digests and chunk words zero."""
+        return _restore_two_calls(lambda mn, dist, li, n, cout: self.ctx.lib.nhip_ms_archive_restore_shape(
+            self._h, _ptr(mn), _ptr(dist), _ptr(li), n, cout), "nhip_ms_archive_restore_shape", index_sets,
+            aocl_leaf_indices)
 
     def _restore(self, index_sets, aocl_leaf_indices):
         _, o = self.restore_raw(index_sets, aocl_leaf_indices)

@@ -329,6 +329,11 @@ pub struct nhip_ms_store_caps {
 /// Load gives a level of an archive's MMRs a launch of its own while the level below has more nodes than this
 /// (`NHIP_MS_ARCHIVE_TAIL_NODES`).
 pub const NHIP_MS_ARCHIVE_TAIL_NODES: usize = 256;
+/// The restore shape kernels' geometry (`nhip_ms_archive_restore_shape`): witnesses per workgroup, items per scan
+/// tile, lanes that carry the tile sums across the grid.
+pub const NHIP_MS_RESTORE_WAVES: usize = 4;
+pub const NHIP_MS_RESTORE_SCAN_WIDTH: usize = 256;
+pub const NHIP_MS_RESTORE_CARRY_LANES: usize = 64;
 
 /// Initial capacities of a device-resident archival mutator set (`nhip_ms_archive_create`; 0: a default).
 #[repr(C)]
@@ -727,6 +732,11 @@ extern "C" {
     pub fn nhip_ms_archive_restore_plan(aocl_leafs: u64, chunk_len: *const u64, n_chunks: u64, minimum: *const u64,
                                         distances: *const u32, aocl_leaf_index: *const u64, n: usize,
                                         out: *mut nhip_ms_updated) -> c_int;
+    pub fn nhip_ms_archive_restore_shape(archive: *mut nhip_ms_archive, minimum: *const u64, distances: *const u32,
+                                         aocl_leaf_index: *const u64, n: usize, out: *mut nhip_ms_updated) -> c_int;
+    pub fn nhip_ms_store_append_restored(store: *mut nhip_ms_store, archive: *mut nhip_ms_archive, minimum: *const u64,
+                                         distances: *const u32, aocl_leaf_index: *const u64, aocl_leaf: *const u64,
+                                         n: usize, status: *mut u8) -> c_int;
     pub fn nhip_blk_ms_params_default(out: *mut nhip_blk_ms_params);
     pub fn nhip_blk_ms_walk(bytes: *const u8, n_bytes: usize, pow_tree_height: u32, blocks: *const nhip_blk_block,
                             n: usize, out: *mut nhip_blk_ms_parts) -> c_int;
